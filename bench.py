@@ -33,6 +33,7 @@ DENSE_ARCH = [512, 256, 128]
 OVER_ARCH = [1024, 1024, 512, 256, 1]
 IDS_PER_FEATURE = 1  # Criteo is one-hot per categorical feature
 LR = 0.05
+SEED = 0  # weight init; the batches are seeded apart (make_host_batches)
 
 
 def scaled_rows(scale: float) -> List[int]:
@@ -133,6 +134,30 @@ class _CyclingIterator:
         return b
 
 
+# --dump-outputs writes at most this many bytes in all
+DUMP_BYTES_CAP = 64 << 20
+
+
+def dump_outputs(out_dir: str, output, rank: int = 0, world: int = 1) -> None:
+    """Write what the last timed step returned to its caller — DLRMTrain's
+    (loss, logits, labels) — as float32 ``<name>.npy`` files
+    (``<name>_rank<r>.npy`` when more than one rank runs). An array too large
+    for its share of DUMP_BYTES_CAP is cut to a fixed, seeded sample of its
+    elements, so two builds still dump the same positions."""
+    import numpy as np
+
+    names = ("loss", "logits", "labels")
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BYTES_CAP // 4 // len(names)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    for name, t in zip(names, output):
+        a = t.detach().float().cpu().numpy().reshape(-1)
+        if a.size > cap:
+            keep = np.random.default_rng(0).choice(a.size, cap, replace=False)
+            a = a[np.sort(keep)]
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def _dense_to_bf16(dmp) -> None:
     """bf16 dense parameters: under autocast the per-layer weight casts
     disappear (saved ~39 cast kernels/step); grads/optimizer run in bf16."""
@@ -174,7 +199,7 @@ def _graph_dense_modules(dmp, batch_size: int, device) -> None:
 
 
 def run_bench(gpus: int, steps: int, warmup: int, batch_size: int, scale: float,
-              qcomm: str = "none") -> None:
+              qcomm: str = "none", dump_dir: str | None = None) -> None:
     import torch.distributed as dist
 
     from torchrec_amd.distributed.model_parallel import DistributedModelParallel
@@ -308,8 +333,9 @@ def run_bench(gpus: int, steps: int, warmup: int, batch_size: int, scale: float,
     step_t: List[float] = []
     t0 = time.perf_counter()
     tprev = t0
+    output = None
     for _ in range(steps):
-        pipeline.progress(it)
+        output = pipeline.progress(it)
         tnow = time.perf_counter()
         step_t.append(tnow - tprev)
         tprev = tnow
@@ -323,6 +349,8 @@ def run_bench(gpus: int, steps: int, warmup: int, batch_size: int, scale: float,
         t = torch.tensor([dt], device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if dump_dir is not None:
+        dump_outputs(dump_dir, output, rank, world)
 
     ms_per_step = dt / steps * 1e3
     samples_per_sec = batch_size * world * steps / dt
@@ -367,7 +395,8 @@ def run_bench(gpus: int, steps: int, warmup: int, batch_size: int, scale: float,
         print(json.dumps(result))
 
 
-def run_graph_bench(steps: int, warmup: int, batch_size: int, scale: float) -> None:
+def run_graph_bench(steps: int, warmup: int, batch_size: int, scale: float,
+                    dump_dir: str | None = None) -> None:
     """Single-GPU hipGraph mode: the whole train step (TBE fwd + dense fwd/bwd +
     fused update + optimizer) is captured once and replayed — Criteo is one-hot
     so every tensor shape is static. Removes ~all launch/Python overhead
@@ -441,13 +470,13 @@ def run_graph_bench(steps: int, warmup: int, batch_size: int, scale: float) -> N
 
     def one_step():
         with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
-            loss, _ = dmp(static_batch)
+            loss, output = dmp(static_batch)
         # set_to_none: backward writes fresh grad buffers (replay-stable via
         # the capture pool) — drops one fill kernel per dense param
         dense_opt.zero_grad(set_to_none=True)
         loss.backward()
         dense_opt.step()
-        return loss
+        return loss, output
 
     # graph warmup on a side stream, then capture
     s = torch.cuda.Stream()
@@ -458,7 +487,7 @@ def run_graph_bench(steps: int, warmup: int, batch_size: int, scale: float) -> N
     torch.cuda.current_stream().wait_stream(s)
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
-        static_loss = one_step()
+        static_loss, static_output = one_step()
 
     # Double-buffered input staging: the H2D of the next batch rides a copy
     # stream, overlapped with the current replay; the main stream only pays
@@ -519,6 +548,10 @@ def run_graph_bench(steps: int, warmup: int, batch_size: int, scale: float) -> N
         tprev = tnow
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump_dir is not None:
+        # the captured step's outputs are static tensors: after the last
+        # replay they hold what that step returned
+        dump_outputs(dump_dir, static_output)
     ms_per_step = dt / steps * 1e3
     result = {
         "metric": "samples/sec (whole node) DLRM Criteo-TB synthetic",
@@ -557,7 +590,8 @@ def run_graph_bench(steps: int, warmup: int, batch_size: int, scale: float) -> N
 
 
 def run_dist_graph_bench(
-    steps: int, warmup: int, batch_size: int, scale: float
+    steps: int, warmup: int, batch_size: int, scale: float,
+    dump_dir: str | None = None,
 ) -> None:
     """Multi-rank hipGraph mode: the WHOLE per-rank train step — KJT a2a,
     lookup, pooled output a2a, dense fwd/bwd, dense-grad all-reduce, both
@@ -646,7 +680,7 @@ def run_dist_graph_bench(
 
     def one_step():
         with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
-            loss, _ = dmp(static_batch)
+            loss, output = dmp(static_batch)
         dense_opt.zero_grad(set_to_none=True)
         loss.backward()
         if world > 1:
@@ -658,7 +692,7 @@ def run_dist_graph_bench(
                 g.copy_(flat[off : off + g.numel()].view_as(g))
                 off += g.numel()
         dense_opt.step()
-        return loss
+        return loss, output
 
     # eager warmup on a side stream: RCCL communicators come up, the KJT a2a
     # splits caches fill (first exchange), allocator pools stabilize
@@ -673,11 +707,11 @@ def run_dist_graph_bench(
     # static splits ON for capture: the cached-splits path is the one with no
     # device->host sync, which stream capture requires
     set_static_kjt_splits(True)
-    static_loss = None
+    static_loss = static_output = None
     try:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            static_loss = one_step()
+            static_loss, static_output = one_step()
         ok = torch.ones(1, device=device)
     except Exception as exc:
         print(f"# rank {rank}: dist capture failed locally: {exc!r}", flush=True)
@@ -749,6 +783,8 @@ def run_dist_graph_bench(
     t = torch.tensor([dt], device=device)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if dump_dir is not None:
+        dump_outputs(dump_dir, static_output, rank, world)
     ms_per_step = dt / steps * 1e3
     result = {
         "metric": "samples/sec (whole node) DLRM Criteo-TB synthetic",
@@ -837,7 +873,26 @@ if __name__ == "__main__":
         choices=["none", "fp16", "bf16", "fp8"],
         help="compress the pooled a2a wire (fwd+bwd)",
     )
+    p.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="after the timed steps, write what the last one returned "
+        "(loss, logits, labels) as DIR/<name>.npy in float32",
+    )
+    p.add_argument(
+        "--full",
+        action="store_true",
+        help="also run the secondary measurements. There are none today: "
+        "every figure this benchmark prints comes from the timed steps "
+        "themselves, so a plain run is already the lean one",
+    )
     args = p.parse_args()
+    if not args.smoke:
+        # weights come from the global generators (batches carry their own):
+        # a fixed seed per rank makes every input, hence --dump-outputs,
+        # repeat from run to run
+        torch.manual_seed(SEED + int(os.environ.get("RANK", "0")))
     # single-GPU default is the hipGraph-captured step (static one-hot shapes;
     # full fwd+bwd+optimizer inside the capture). TREC_NO_HIPGRAPH=1 or any
     # capture failure falls back to the stream-pipelined eager path.
@@ -877,14 +932,15 @@ if __name__ == "__main__":
         if torch.cuda.is_available():
             torch.cuda.empty_cache()
         run_bench(args.gpus, args.steps, args.warmup, args.batch_size,
-                  args.scale, qcomm=args.qcomm)
+                  args.scale, qcomm=args.qcomm, dump_dir=args.dump_outputs)
 
     if args.smoke:
         run_smoke()
     elif want_graph and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         failed = None
         try:
-            run_graph_bench(args.steps, args.warmup, args.batch_size, args.scale)
+            run_graph_bench(args.steps, args.warmup, args.batch_size, args.scale,
+                            dump_dir=args.dump_outputs)
         except Exception as exc:  # pragma: no cover — capture fallback
             failed = repr(exc)
         if failed is not None:
@@ -893,7 +949,8 @@ if __name__ == "__main__":
     elif want_dist_graph:
         failed = None
         try:
-            run_dist_graph_bench(args.steps, args.warmup, args.batch_size, args.scale)
+            run_dist_graph_bench(args.steps, args.warmup, args.batch_size,
+                                 args.scale, dump_dir=args.dump_outputs)
         except Exception as exc:  # pragma: no cover — capture fallback
             failed = repr(exc)
         if failed is not None:
@@ -901,4 +958,4 @@ if __name__ == "__main__":
                 f"# dist hipGraph capture failed ({failed}); eager pipeline fallback")
     else:
         run_bench(args.gpus, args.steps, args.warmup, args.batch_size, args.scale,
-                  qcomm=args.qcomm)
+                  qcomm=args.qcomm, dump_dir=args.dump_outputs)

@@ -54,8 +54,11 @@ def test_batch_is_pipelineable():
     assert isinstance(b, Pipelineable) and isinstance(b, Multistreamable)
     b2 = b.to(torch.device("cpu"), non_blocking=False)
     assert torch.equal(b2.dense_features, b.dense_features)
-    # record_stream on CPU tensors is a no-op but must not raise on the
-    # contract surface (GPU pipelines call it on every batch)
+    # the contract surface exists everywhere; the call itself is only
+    # defined for device tensors (torch raises for a CPU tensor), and GPU
+    # pipelines make it on every batch once it is on the device
     assert callable(getattr(b, "record_stream"))
     if torch.cuda.is_available():  # pragma: no cover — GPU-only contract call
-        b.record_stream(torch.cuda.current_stream())
+        b3 = b.to(torch.device("cuda"), non_blocking=False)
+        assert torch.equal(b3.dense_features.cpu(), b.dense_features)
+        b3.record_stream(torch.cuda.current_stream())
