@@ -137,27 +137,65 @@ def bench_col_sum(M=8192, N=1024):
     }))
 
 
-def bench_quant_tbe(B=8192, D=128, tables=26, rows=100_000):
-    """int8 inference TBE vs fp32 training TBE forward."""
-    from torchrec_amd.quant.embedding_modules import QuantTableBatchedEmbeddingBags
+def bench_quant_tbe(B=8192, D=128, tables=26, rows=100_000, weight_dtype=None, repeats=1):
+    """Quantized inference TBE forward at ``weight_dtype`` (default INT8) vs
+    the fp32 training TBE forward. Returns the ``repeats`` timings in us."""
+    from torchrec_amd.modules.embedding_configs import DATA_TYPE_NUM_BITS, DataType
+    from torchrec_amd.quant.embedding_modules import (
+        QuantTableBatchedEmbeddingBags,
+        nbit_row_stride,
+    )
     from torchrec_amd.ops.tbe import TableBatchedEmbeddingBags
 
+    weight_dtype = weight_dtype or DataType.INT8
+    name = weight_dtype.name.lower()
     torch.manual_seed(0)
     specs = [(f"t{i}", rows, D) for i in range(tables)]
-    q = QuantTableBatchedEmbeddingBags(specs, device=torch.device("cuda"))
+    q = QuantTableBatchedEmbeddingBags(
+        specs, device=torch.device("cuda"), weight_dtypes=[weight_dtype] * tables
+    )
     for i in range(tables):
         q.load_float_table(i, torch.randn(rows, D, device="cuda"))
-    f32 = TableBatchedEmbeddingBags(specs, device=torch.device("cuda"))
     F = tables
     indices = torch.randint(0, rows, (F * B,)).cuda()
     offsets = torch.arange(F * B + 1, dtype=torch.int64).cuda()
-    qt = _time_kernel(lambda: q(indices, offsets))
-    ft = _time_kernel(lambda: f32(indices, offsets))
-    print(json.dumps({
-        "bench": "quant_tbe_fwd", "B": B, "tables": tables, "D": D,
-        "int8_us": round(qt, 1), "fp32_us": round(ft, 1),
-        "int8_qps_m": round(B / qt, 1),
-    }))
+    # 5000 launches per timing: a window long enough not to measure the clock
+    times = [
+        _time_kernel(lambda: q(indices, offsets), iters=5000, warmup=20) for _ in range(repeats)
+    ]
+    qt = sorted(times)[len(times) // 2]
+    res = {
+        "bench": "quant_tbe_fwd", "weight_dtype": weight_dtype.name, "B": B,
+        "tables": tables, "D": D,
+        "row_bytes": nbit_row_stride(D, DATA_TYPE_NUM_BITS[weight_dtype]),
+        f"{name}_us": round(qt, 1), f"{name}_qps_m": round(B / qt, 1),
+    }
+    if repeats > 1:
+        res[f"{name}_us_runs"] = [round(t, 1) for t in times]
+        res[f"{name}_spread_us"] = round(max(times) - min(times), 1)
+    if weight_dtype == DataType.INT8:
+        f32 = TableBatchedEmbeddingBags(specs, device=torch.device("cuda"))
+        res["fp32_us"] = round(_time_kernel(lambda: f32(indices, offsets)), 1)
+    print(json.dumps(res))
+    return times
+
+
+def bench_quant_suite():
+    """INT8 five times (median + max-min spread = the noise margin), then INT4
+    and INT2, all in this process."""
+    from torchrec_amd.modules.embedding_configs import DataType
+
+    int8 = bench_quant_tbe(weight_dtype=DataType.INT8, repeats=5)
+    med, spread = sorted(int8)[2], max(int8) - min(int8)
+    for dt in (DataType.INT4, DataType.INT2):
+        t = bench_quant_tbe(weight_dtype=dt, repeats=3)
+        t_med = sorted(t)[1]
+        print(json.dumps({
+            "bench": "quant_tbe_fwd_vs_int8", "weight_dtype": dt.name,
+            "us": round(t_med, 1), "int8_median_us": round(med, 1),
+            "int8_spread_us": round(spread, 1),
+            "within_noise_or_faster": bool(t_med <= med + spread),
+        }))
 
 
 if __name__ == "__main__":
@@ -185,4 +223,4 @@ if __name__ == "__main__":
     if a.suite in ("all", "col_sum"):
         bench_col_sum()
     if a.suite in ("all", "quant"):
-        bench_quant_tbe()
+        bench_quant_suite()

@@ -54,7 +54,8 @@ class ShardedTableLocal:
     full_dim: int = 0
     full_rows: int = 0
     use_sum_kernel: bool = False  # RW mean: kernel sums, divisor applied later
-    data_type: str = "FP32"  # weights precision (DataType.name): FP32/FP16/BF16
+    # weights precision (DataType.name): FP32/FP16/BF16; INT8/INT4/INT2 for quant
+    data_type: str = "FP32"
 
 
 def group_tables_by_kernel(
@@ -117,8 +118,10 @@ class GroupedPooledEmbeddingsLookup(nn.Module):
             if group[0].kernel == EmbeddingComputeKernel.QUANT.value:
                 from torchrec_amd.quant.embedding_modules import (
                     QuantTableBatchedEmbeddingBags,
+                    quant_data_type,
                 )
 
+                # groups are keyed by data_type: one width per quant group
                 qtbe = QuantTableBatchedEmbeddingBags(
                     [(t.name, t.local_rows, t.local_dim) for t in group],
                     feature_table_map=[
@@ -126,6 +129,7 @@ class GroupedPooledEmbeddingsLookup(nn.Module):
                     ],
                     pooling=pool,
                     device=device,
+                    weight_dtypes=[quant_data_type(t.data_type) for t in group],
                 )
                 self._emb_modules.append(qtbe)
                 self._feature_splits.append(

@@ -2,7 +2,8 @@
 
 Reference parity: torchrec/distributed/quant_embedding.py
 (ShardedQuantEmbeddingCollection) — the training sequence dists (feature a2a
-in, per-row embedding a2a out) reused over int8 nbit sequence lookups."""
+in, per-row embedding a2a out) reused over the rowwise-quantized
+(INT8/INT4/INT2 per table) sequence lookups."""
 
 from __future__ import annotations
 
@@ -22,12 +23,12 @@ from torchrec_amd.distributed.types import (
 from torchrec_amd.quant.embedding_modules import (
     EmbeddingCollection as QuantEmbeddingCollection,
     QuantTableBatchedEmbeddingBags,
+    quant_data_type,
 )
-from torchrec_amd import ops
 
 
 class _QuantSeqLookup(nn.Module):
-    """Sequence (per-row) int8 lookup over a quant TBE group."""
+    """Sequence (per-row) quantized lookup over a quant TBE group."""
 
     def __init__(self, qtbe: QuantTableBatchedEmbeddingBags, dim: int) -> None:
         super().__init__()
@@ -39,28 +40,15 @@ class _QuantSeqLookup(nn.Module):
         F = qtbe._num_features
         B = (offsets.numel() - 1) // max(F, 1)
         if qtbe.qweights.is_cuda or qtbe.qweights.is_pinned():
-            ops.hip_ops()
             feat_val_offsets = offsets[::B][: F + 1].contiguous()
             if feat_val_offsets.numel() < F + 1:
                 feat_val_offsets = torch.cat([feat_val_offsets, offsets[-1:]])
-            return torch.ops.trec_amd.tbe_forward_seq_int8(
-                qtbe.qweights,
-                qtbe._table_byte_offsets,
-                qtbe._dims_t,
-                qtbe._feat_table_t,
-                feat_val_offsets,
-                indices,
-                self._dim,
-                qtbe._max_D,
-            )
+            return qtbe.forward_sequence(indices, feat_val_offsets, self._dim)
         # CPU reference: dequantize rows per feature
-        from torchrec_amd.quant.embedding_modules import dequantize_rowwise_int8
-
         outs: List[torch.Tensor] = []
         for f in range(F):
             t = qtbe._feature_table_map[f]
-            name, rows, dim = qtbe._specs[t]
-            w = dequantize_rowwise_int8(qtbe.packed_table(t), dim)
+            w = qtbe.dequantized_table(t)
             lo, hi = int(offsets[f * B]), int(offsets[(f + 1) * B])
             outs.append(w[indices[lo:hi]])
         return (
@@ -112,6 +100,7 @@ class ShardedQuantEmbeddingCollection(ShardedEmbeddingCollection):
             [(t.name, max(t.local_rows, 1), t.local_dim) for t in tables],
             feature_table_map=[i for i, t in enumerate(tables) for _ in t.feature_names],
             device=self._quant_device_pre,
+            weight_dtypes=[quant_data_type(t.data_type) for t in tables],
         )
         return _QuantSeqLookup(qtbe, D)
 

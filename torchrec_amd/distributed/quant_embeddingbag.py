@@ -3,7 +3,8 @@
 Reference parity: torchrec/distributed/quant_embeddingbag.py
 (ShardedQuantEmbeddingBagCollection) and the infer shardings
 (tw_sharding.py:543 InferTwEmbeddingSharding): the training dists are reused
-(one process per GPU over RCCL/xGMI); lookups run the int8 nbit TBE.
+(one process per GPU over RCCL/xGMI); lookups run the quantized TBE at each
+table's own width (INT8/INT4/INT2).
 """
 
 from __future__ import annotations
@@ -29,7 +30,8 @@ from torchrec_amd.quant.embedding_modules import (
 
 
 class ShardedQuantEmbeddingBagCollection(ShardedEmbeddingBagCollection):
-    """Shards a quantized EBC; packed int8 rows are sliced per shard."""
+    """Shards a quantized EBC; packed rows (any width: the slice is by whole
+    rows at the table's own stride) are sliced per shard."""
 
     def __init__(
         self,

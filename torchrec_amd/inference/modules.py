@@ -12,6 +12,7 @@ from typing import Any, Dict, List, Optional, Tuple, Type
 import torch
 import torch.nn as nn
 
+from torchrec_amd.modules.embedding_configs import DataType
 from torchrec_amd.modules.embedding_modules import (
     EmbeddingBagCollection as FloatEBC,
     EmbeddingCollection as FloatEC,
@@ -26,9 +27,13 @@ def quantize_inference_model(
     model: nn.Module,
     quantization_mapping: Optional[Dict[Type[nn.Module], Any]] = None,
     output_dtype: torch.dtype = torch.float32,
+    weight_dtype: DataType = DataType.INT8,
+    per_table_weight_dtype: Optional[Dict[str, DataType]] = None,
 ) -> nn.Module:
-    """Swap float embedding modules for int8 quantized ones in-place
-    (reference inference/modules.py:372)."""
+    """Swap float embedding modules for rowwise-quantized ones in-place
+    (reference inference/modules.py:372). Tables are packed at
+    ``weight_dtype`` (INT8/INT4/INT2) unless ``per_table_weight_dtype`` names
+    another width for them."""
     mapping = quantization_mapping or {
         FloatEBC: QuantEBC,
         FloatEC: QuantEC,
@@ -38,7 +43,17 @@ def quantize_inference_model(
         for name, child in list(parent.named_children()):
             qcls = mapping.get(type(child))
             if qcls is not None:
-                setattr(parent, name, qcls.from_float(child, output_dtype=output_dtype))
+                if weight_dtype == DataType.INT8 and not per_table_weight_dtype:
+                    # custom mappings only need the original from_float signature
+                    q = qcls.from_float(child, output_dtype=output_dtype)
+                else:
+                    q = qcls.from_float(
+                        child,
+                        output_dtype=output_dtype,
+                        weight_dtype=weight_dtype,
+                        per_table_weight_dtype=per_table_weight_dtype,
+                    )
+                setattr(parent, name, q)
             else:
                 _swap(child)
 

@@ -31,6 +31,7 @@ class DataType(Enum):
     BF16 = "BF16"
     INT8 = "INT8"
     INT4 = "INT4"
+    INT2 = "INT2"
 
     def __str__(self) -> str:
         return self.value
@@ -42,6 +43,7 @@ DATA_TYPE_NUM_BITS: Dict[DataType, int] = {
     DataType.BF16: 16,
     DataType.INT8: 8,
     DataType.INT4: 4,
+    DataType.INT2: 2,
 }
 
 
@@ -52,6 +54,7 @@ def data_type_to_dtype(data_type: DataType) -> torch.dtype:
         DataType.BF16: torch.bfloat16,
         DataType.INT8: torch.uint8,
         DataType.INT4: torch.uint8,
+        DataType.INT2: torch.uint8,
     }[data_type]
 
 

@@ -109,6 +109,19 @@ at::Tensor tbe_forward_seq_int8(const at::Tensor& qweights,
                                 const at::Tensor& feat_table,
                                 const at::Tensor& feat_val_offsets, const at::Tensor& indices,
                                 int64_t D_out, int64_t max_D);
+at::Tensor quantize_rowwise_nbit(const at::Tensor& weights, int64_t bits);
+at::Tensor tbe_forward_pooled_nbit(const at::Tensor& qweights,
+                                   const at::Tensor& table_byte_offsets, const at::Tensor& dims,
+                                   const at::Tensor& weight_bits, const at::Tensor& feat_table,
+                                   const at::Tensor& d_out_offsets, const at::Tensor& indices,
+                                   const at::Tensor& offsets,
+                                   const at::Tensor& per_sample_weights, int64_t B,
+                                   int64_t total_D, int64_t max_units, bool mean_pool);
+at::Tensor tbe_forward_seq_nbit(const at::Tensor& qweights,
+                                const at::Tensor& table_byte_offsets, const at::Tensor& dims,
+                                const at::Tensor& weight_bits, const at::Tensor& feat_table,
+                                const at::Tensor& feat_val_offsets, const at::Tensor& indices,
+                                int64_t D_out, int64_t max_units);
 
 // interaction.hip
 at::Tensor col_sum(const at::Tensor& input);
@@ -224,6 +237,16 @@ TORCH_LIBRARY(trec_amd, m) {
       "tbe_forward_seq_int8(Tensor qweights, Tensor table_byte_offsets, Tensor dims,"
       " Tensor feat_table, Tensor feat_val_offsets, Tensor indices, int D_out, int max_D)"
       " -> Tensor");
+  m.def("quantize_rowwise_nbit(Tensor weights, int bits) -> Tensor");
+  m.def(
+      "tbe_forward_pooled_nbit(Tensor qweights, Tensor table_byte_offsets, Tensor dims,"
+      " Tensor weight_bits, Tensor feat_table, Tensor d_out_offsets, Tensor indices,"
+      " Tensor offsets, Tensor per_sample_weights, int B, int total_D, int max_units,"
+      " bool mean_pool) -> Tensor");
+  m.def(
+      "tbe_forward_seq_nbit(Tensor qweights, Tensor table_byte_offsets, Tensor dims,"
+      " Tensor weight_bits, Tensor feat_table, Tensor feat_val_offsets, Tensor indices,"
+      " int D_out, int max_units) -> Tensor");
   m.def("col_sum(Tensor input) -> Tensor");
   m.def("interaction_forward(Tensor dense, Tensor sparse, Tensor pi, Tensor pj) -> Tensor");
   m.def("relu_bwd_col_sum(Tensor grad_out, Tensor y) -> (Tensor, Tensor)");
@@ -271,6 +294,9 @@ TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
   m.impl("quantize_rowwise_int8", trec_amd::quantize_rowwise_int8);
   m.impl("tbe_forward_pooled_int8", trec_amd::tbe_forward_pooled_int8);
   m.impl("tbe_forward_seq_int8", trec_amd::tbe_forward_seq_int8);
+  m.impl("quantize_rowwise_nbit", trec_amd::quantize_rowwise_nbit);
+  m.impl("tbe_forward_pooled_nbit", trec_amd::tbe_forward_pooled_nbit);
+  m.impl("tbe_forward_seq_nbit", trec_amd::tbe_forward_seq_nbit);
   m.impl("col_sum", trec_amd::col_sum);
   m.impl("interaction_forward", trec_amd::interaction_forward);
   m.impl("relu_bwd_col_sum", trec_amd::relu_bwd_col_sum);

@@ -1,4 +1,5 @@
-// INT8 rowwise-quantized inference TBE for MI355X (gfx950).
+// Rowwise-quantized inference TBE for MI355X (gfx950): the INT8 kernels, and
+// below them the n-bit (INT8/INT4/INT2, mixed per table) kernels.
 //
 // MI355X-native equivalent of the reference's IntNBitTableBatchedEmbeddingBags
 // (reference torchrec/distributed/quant_embedding_kernel.py:237; kernel spec:
@@ -247,6 +248,340 @@ at::Tensor tbe_forward_seq_int8(
     default: TBE_QS_LAUNCH(64, 8); break;
   }
 #undef TBE_QS_LAUNCH
+  return out;
+}
+
+// ===========================================================================
+// n-bit rows (INT8 / INT4 / INT2), mixed per table in one launch.
+//
+// Row = [codes: D*bits/8 B][fp16 scale][fp16 bias][zero pad], stride rounded
+// up to 16 B; D*bits % 32 == 0 so a row is a whole number of 32-bit code
+// words. Element e sits at bit (e*bits)%32 of word e*bits/32, low bits first.
+// For bits == 8 this is byte-for-byte the INT8 format above.
+// ===========================================================================
+
+__host__ __device__ inline int64_t nbit_row_stride(int code_bytes) {
+  return ((code_bytes + 4 /*scale+bias*/ + 15) / 16) * 16;
+}
+
+template <int BITS>
+__device__ __forceinline__ void quantize_row_nbit(const float* __restrict__ row, int D,
+                                                  uint8_t* __restrict__ orow, int64_t stride,
+                                                  int l) {
+  constexpr int EPW = 32 / BITS;
+  constexpr float kLevels = static_cast<float>((1 << BITS) - 1);
+  float mn = INFINITY, mx = -INFINITY;
+  for (int d = l; d < D; d += kWaveSize) {
+    float v = row[d];
+    mn = fminf(mn, v);
+    mx = fmaxf(mx, v);
+  }
+#pragma unroll
+  for (int off = kWaveSize / 2; off > 0; off >>= 1) {
+    mn = fminf(mn, __shfl_xor(mn, off, kWaveSize));
+    mx = fmaxf(mx, __shfl_xor(mx, off, kWaveSize));
+  }
+  // codes are taken against the STORED fp16 scale/bias: at 4 and 2 bits the
+  // fp16 rounding is no longer small next to a step
+  __half scale_h = __float2half((mx - mn) / kLevels);
+  __half bias_h = __float2half(mn);
+  float scale = __half2float(scale_h);
+  float bias = __half2float(bias_h);
+  int n_words = D / EPW;
+  uint32_t* owords = reinterpret_cast<uint32_t*>(orow);
+  for (int wi = l; wi < n_words; wi += kWaveSize) {
+    uint32_t word = 0;
+    if (scale != 0.f) {
+#pragma unroll
+      for (int j = 0; j < EPW; ++j) {
+        float q = floorf((row[wi * EPW + j] - bias) / scale + 0.5f);
+        q = fminf(fmaxf(q, 0.f), kLevels);
+        word |= static_cast<uint32_t>(q) << (j * BITS);
+      }
+    }
+    owords[wi] = word;
+  }
+  if (l == 0) {
+    __half* sb = reinterpret_cast<__half*>(owords + n_words);
+    sb[0] = scale_h;
+    sb[1] = bias_h;
+  }
+  // padding is part of the packed buffer (state dicts, RW row slices): zero it
+  int n_pad = static_cast<int>(stride / 4) - n_words - 1;
+  for (int k = l; k < n_pad; k += kWaveSize) owords[n_words + 1 + k] = 0u;
+}
+
+template <int BITS>
+__global__ void quantize_rowwise_nbit_kernel(const float* __restrict__ w, int64_t R, int D,
+                                             int64_t stride, uint8_t* __restrict__ out) {
+  // one wave per row
+  int64_t wave = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWaveSize;
+  int64_t n_waves = (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWaveSize;
+  int l = lane_id();
+  for (int64_t r = wave; r < R; r += n_waves)
+    quantize_row_nbit<BITS>(w + r * D, D, out + r * stride, stride, l);
+}
+
+at::Tensor quantize_rowwise_nbit(const at::Tensor& weights, int64_t bits) {
+  TORCH_CHECK(weights.is_cuda() && weights.dim() == 2 && weights.scalar_type() == at::kFloat);
+  TORCH_CHECK(bits == 4 || bits == 2, "quantize_rowwise_nbit: bits must be 4 or 2, got ", bits);
+  int64_t R = weights.size(0);
+  int D = weights.size(1);
+  TORCH_CHECK((static_cast<int64_t>(D) * bits) % 32 == 0, "quantize_rowwise_nbit: D*bits (",
+              D, "*", bits, ") must be a multiple of 32");
+  int64_t stride = nbit_row_stride(static_cast<int>(D * bits / 8));
+  auto out = at::empty({R, stride}, weights.options().dtype(at::kByte));
+  if (R == 0) return out;
+  auto w = weights.contiguous();
+  int grid = grid_for(R * kWaveSize, kBlockThreads);
+  if (bits == 4)
+    hipLaunchKernelGGL(quantize_rowwise_nbit_kernel<4>, dim3(grid), dim3(kBlockThreads), 0,
+                       q_stream(), w.data_ptr<float>(), R, D, stride, out.data_ptr<uint8_t>());
+  else
+    hipLaunchKernelGGL(quantize_rowwise_nbit_kernel<2>, dim3(grid), dim3(kBlockThreads), 0,
+                       q_stream(), w.data_ptr<float>(), R, D, stride, out.data_ptr<uint8_t>());
+  return out;
+}
+
+// Lane mapping. A lane owns one code unit of every row per chunk: the 32-bit
+// word at INT8 (4 columns) and INT4 (8 columns), the 16-bit half-word at INT2
+// (8 columns). A lane that owned a whole INT2 word would store four float4 at
+// a 64 B lane stride; that form measured 39 us against INT8's 33.5 us at the
+// bench shape, so no lane owns more than 8 columns (32 B, two float4).
+template <int BITS>
+struct CodeUnit {
+  static constexpr int kCols = BITS == 8 ? 4 : 8;  // output columns per lane
+  static constexpr int kBits = kCols * BITS;       // 32, 32, 16
+  __device__ static __forceinline__ uint32_t load(const uint8_t* __restrict__ row, int ui) {
+    if constexpr (kBits == 32) return reinterpret_cast<const uint32_t*>(row)[ui];
+    else return reinterpret_cast<const uint16_t*>(row)[ui];
+  }
+};
+
+// One lane's share of a bag. BITS is a template parameter so the accumulators
+// stay in registers; the caller switches on the bag's table.
+template <int BITS, int LPS, int CHUNKS>
+__device__ __forceinline__ void pool_bag_nbit(
+    const uint8_t* __restrict__ tab, int D, const int64_t* __restrict__ indices,
+    const float* __restrict__ psw, int64_t i0, int64_t i1, bool mean_pool,
+    float* __restrict__ orow, int sl) {
+  constexpr int COLS = CodeUnit<BITS>::kCols;
+  constexpr uint32_t kMask = (1u << BITS) - 1u;
+  int code_bytes = D * BITS / 8;
+  int n_units = D / COLS;
+  int64_t stride = nbit_row_stride(code_bytes);
+  float acc[CHUNKS][COLS];
+#pragma unroll
+  for (int c = 0; c < CHUNKS; ++c)
+#pragma unroll
+    for (int j = 0; j < COLS; ++j) acc[c][j] = 0.f;
+  for (int64_t i = i0; i < i1; ++i) {
+    const uint8_t* row = tab + indices[i] * stride;
+    // same address across the slot: one broadcast load
+    const __half* sb = reinterpret_cast<const __half*>(row + code_bytes);
+    float scale = __half2float(sb[0]);
+    float bias = __half2float(sb[1]);
+    float w = psw ? psw[i] : 1.f;
+#pragma unroll
+    for (int c = 0; c < CHUNKS; ++c) {
+      int ui = c * LPS + sl;
+      if (ui < n_units) {
+        uint32_t unit = CodeUnit<BITS>::load(row, ui);
+#pragma unroll
+        for (int j = 0; j < COLS; ++j) {
+          float q = static_cast<float>((unit >> (j * BITS)) & kMask);
+          acc[c][j] += w * (q * scale + bias);
+        }
+      }
+    }
+  }
+  float s = 1.f;
+  if (mean_pool && i1 > i0) s = 1.f / static_cast<float>(i1 - i0);
+  float4* o4 = reinterpret_cast<float4*>(orow);
+#pragma unroll
+  for (int c = 0; c < CHUNKS; ++c) {
+    int ui = c * LPS + sl;
+    if (ui < n_units) {
+#pragma unroll
+      for (int k = 0; k < COLS / 4; ++k)
+        o4[ui * (COLS / 4) + k] =
+            make_float4(acc[c][4 * k] * s, acc[c][4 * k + 1] * s, acc[c][4 * k + 2] * s,
+                        acc[c][4 * k + 3] * s);
+    }
+  }
+}
+
+template <int LPS, int CHUNKS>
+__global__ void __launch_bounds__(kBlockThreads) tbe_fwd_pooled_nbit_kernel(
+    const uint8_t* __restrict__ qweights,
+    const int64_t* __restrict__ table_byte_offsets,  // [T]
+    const int32_t* __restrict__ dims,                // [T]
+    const int32_t* __restrict__ weight_bits,         // [T] 8 / 4 / 2
+    const int32_t* __restrict__ feat_table,          // [F]
+    const int64_t* __restrict__ d_out_offsets,       // [F+1]
+    const int64_t* __restrict__ indices,
+    const int64_t* __restrict__ offsets,  // [F*B+1]
+    const float* __restrict__ psw, int F, int B, int64_t total_D, bool mean_pool,
+    float* __restrict__ out) {
+  int sl = threadIdx.x % LPS;
+  int64_t slot = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / LPS;
+  int64_t n_slots = (static_cast<int64_t>(gridDim.x) * blockDim.x) / LPS;
+  int64_t n_bags = static_cast<int64_t>(F) * B;
+  for (int64_t bag = slot; bag < n_bags; bag += n_slots) {
+    int f = bag / B;
+    int b = bag - static_cast<int64_t>(f) * B;
+    int t = feat_table[f];
+    int bits = weight_bits[t];
+    int D = dims[t];
+    const uint8_t* tab = qweights + table_byte_offsets[t];
+    float* orow = out + static_cast<int64_t>(b) * total_D + d_out_offsets[f];
+    int64_t i0 = offsets[bag], i1 = offsets[bag + 1];
+    // bits is uniform within a slot; a wave diverges only where neighbouring
+    // slots sit on a boundary between tables of different width. A slot
+    // covers units [0, LPS*CHUNKS); lanes past this row's own unit count (a
+    // narrow table in a module whose max is large) load and store nothing.
+    if (bits == 8)
+      pool_bag_nbit<8, LPS, CHUNKS>(tab, D, indices, psw, i0, i1, mean_pool, orow, sl);
+    else if (bits == 4)
+      pool_bag_nbit<4, LPS, CHUNKS>(tab, D, indices, psw, i0, i1, mean_pool, orow, sl);
+    else
+      pool_bag_nbit<2, LPS, CHUNKS>(tab, D, indices, psw, i0, i1, mean_pool, orow, sl);
+  }
+}
+
+// slot width / chunk count from the widest row in lane units (CodeUnit:
+// D/4 at INT8, D/8 at INT4 and INT2)
+#define TBE_NBIT_DISPATCH(LAUNCH, max_units)                    \
+  do {                                                          \
+    if ((max_units) <= 8) LAUNCH(8, 1);                         \
+    else if ((max_units) <= 16) LAUNCH(16, 1);                  \
+    else if ((max_units) <= 32) LAUNCH(32, 1);                  \
+    else if ((max_units) <= 64) LAUNCH(64, 1);                  \
+    else if ((max_units) <= 128) LAUNCH(64, 2);                 \
+    else if ((max_units) <= 256) LAUNCH(64, 4);                 \
+    else LAUNCH(64, 8);                                         \
+  } while (0)
+
+static inline int nbit_lps(int64_t max_units) {
+  return max_units <= 8 ? 8 : (max_units <= 16 ? 16 : (max_units <= 32 ? 32 : 64));
+}
+
+static void check_nbit_args(const at::Tensor& qweights, const at::Tensor& dims,
+                            const at::Tensor& weight_bits, int64_t max_units) {
+  TORCH_CHECK((qweights.is_cuda() || qweights.is_pinned()) && qweights.scalar_type() == at::kByte);
+  TORCH_CHECK(weight_bits.scalar_type() == at::kInt && weight_bits.numel() == dims.numel(),
+              "weight_bits must be int32 [T]");
+  TORCH_CHECK(max_units >= 1 && max_units <= 512,
+              "n-bit TBE rows must be 1..512 lane units (D/4 at INT8, D/8 at INT4/INT2), got ",
+              max_units);
+}
+
+at::Tensor tbe_forward_pooled_nbit(
+    const at::Tensor& qweights, const at::Tensor& table_byte_offsets, const at::Tensor& dims,
+    const at::Tensor& weight_bits, const at::Tensor& feat_table,
+    const at::Tensor& d_out_offsets, const at::Tensor& indices, const at::Tensor& offsets,
+    const at::Tensor& per_sample_weights, int64_t B, int64_t total_D, int64_t max_units,
+    bool mean_pool) {
+  check_nbit_args(qweights, dims, weight_bits, max_units);
+  // every table's D*bits % 32 == 0 makes D % 4 == 0, so rows store as float4
+  TORCH_CHECK(total_D % 4 == 0, "n-bit TBE needs D*bits % 32 == 0 for every table");
+  int F = feat_table.numel();
+  auto out = at::empty({B, total_D}, indices.options().dtype(at::kFloat));
+  if (B == 0 || F == 0) return out;
+  const float* psw_ptr =
+      per_sample_weights.numel() > 0 ? per_sample_weights.data_ptr<float>() : nullptr;
+  auto stream = q_stream();
+  int grid = grid_for(static_cast<int64_t>(F) * B * nbit_lps(max_units), kBlockThreads);
+#define TBE_NB_LAUNCH(LPS, CHUNKS)                                                        \
+  hipLaunchKernelGGL((tbe_fwd_pooled_nbit_kernel<LPS, CHUNKS>), dim3(grid),               \
+                     dim3(kBlockThreads), 0, stream, uvm_ptr<uint8_t>(qweights),           \
+                     table_byte_offsets.data_ptr<int64_t>(), dims.data_ptr<int32_t>(),    \
+                     weight_bits.data_ptr<int32_t>(), feat_table.data_ptr<int32_t>(),     \
+                     d_out_offsets.data_ptr<int64_t>(), indices.data_ptr<int64_t>(),      \
+                     offsets.data_ptr<int64_t>(), psw_ptr, F, (int)B, total_D, mean_pool, \
+                     out.data_ptr<float>())
+  TBE_NBIT_DISPATCH(TBE_NB_LAUNCH, max_units);
+#undef TBE_NB_LAUNCH
+  return out;
+}
+
+// sequence n-bit forward: out[n] = dequant(row(idx[n])), same lane mapping
+template <int BITS, int LPS, int CHUNKS>
+__device__ __forceinline__ void dequant_row_nbit(const uint8_t* __restrict__ row, int D,
+                                                 int D_out, float* __restrict__ orow, int sl) {
+  constexpr int COLS = CodeUnit<BITS>::kCols;
+  constexpr uint32_t kMask = (1u << BITS) - 1u;
+  const __half* sb = reinterpret_cast<const __half*>(row + D * BITS / 8);
+  float scale = __half2float(sb[0]);
+  float bias = __half2float(sb[1]);
+  // an output row holds D_out columns: never store past it
+  int n_units = min(D, D_out) / COLS;
+  float4* o4 = reinterpret_cast<float4*>(orow);
+#pragma unroll
+  for (int c = 0; c < CHUNKS; ++c) {
+    int ui = c * LPS + sl;
+    if (ui < n_units) {
+      uint32_t unit = CodeUnit<BITS>::load(row, ui);
+#pragma unroll
+      for (int k = 0; k < COLS / 4; ++k) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          v[j] = static_cast<float>((unit >> ((4 * k + j) * BITS)) & kMask) * scale + bias;
+        o4[ui * (COLS / 4) + k] = make_float4(v[0], v[1], v[2], v[3]);
+      }
+    }
+  }
+}
+
+template <int LPS, int CHUNKS>
+__global__ void __launch_bounds__(kBlockThreads) tbe_fwd_seq_nbit_kernel(
+    const uint8_t* __restrict__ qweights, const int64_t* __restrict__ table_byte_offsets,
+    const int32_t* __restrict__ dims, const int32_t* __restrict__ weight_bits,
+    const int32_t* __restrict__ feat_table, const int64_t* __restrict__ feat_val_offsets,
+    const int64_t* __restrict__ indices, int F, int64_t N, int D_out,
+    float* __restrict__ out) {
+  int sl = threadIdx.x % LPS;
+  int64_t slot = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / LPS;
+  int64_t n_slots = (static_cast<int64_t>(gridDim.x) * blockDim.x) / LPS;
+  for (int64_t n = slot; n < N; n += n_slots) {
+    int f = upper_bound_segment(feat_val_offsets, F, n);
+    int t = feat_table[f];
+    int bits = weight_bits[t];
+    int D = dims[t];
+    const uint8_t* row =
+        qweights + table_byte_offsets[t] + indices[n] * nbit_row_stride(D * bits / 8);
+    float* orow = out + n * D_out;
+    if (bits == 8) dequant_row_nbit<8, LPS, CHUNKS>(row, D, D_out, orow, sl);
+    else if (bits == 4) dequant_row_nbit<4, LPS, CHUNKS>(row, D, D_out, orow, sl);
+    else dequant_row_nbit<2, LPS, CHUNKS>(row, D, D_out, orow, sl);
+  }
+}
+
+at::Tensor tbe_forward_seq_nbit(
+    const at::Tensor& qweights, const at::Tensor& table_byte_offsets, const at::Tensor& dims,
+    const at::Tensor& weight_bits, const at::Tensor& feat_table,
+    const at::Tensor& feat_val_offsets, const at::Tensor& indices, int64_t D_out,
+    int64_t max_units) {
+  check_nbit_args(qweights, dims, weight_bits, max_units);
+  TORCH_CHECK(D_out % 4 == 0 && D_out <= 4096,
+              "n-bit TBE needs D*bits % 32 == 0 for every table");
+  int64_t N = indices.numel();
+  auto out = at::empty({N, D_out}, indices.options().dtype(at::kFloat));
+  if (N == 0) return out;
+  int F = feat_table.numel();
+  auto stream = q_stream();
+  int grid = grid_for(N * nbit_lps(max_units), kBlockThreads);
+#define TBE_NBS_LAUNCH(LPS, CHUNKS)                                                       \
+  hipLaunchKernelGGL((tbe_fwd_seq_nbit_kernel<LPS, CHUNKS>), dim3(grid),                  \
+                     dim3(kBlockThreads), 0, stream, uvm_ptr<uint8_t>(qweights),           \
+                     table_byte_offsets.data_ptr<int64_t>(), dims.data_ptr<int32_t>(),    \
+                     weight_bits.data_ptr<int32_t>(), feat_table.data_ptr<int32_t>(),     \
+                     feat_val_offsets.data_ptr<int64_t>(), indices.data_ptr<int64_t>(), F, \
+                     N, (int)D_out, out.data_ptr<float>())
+  TBE_NBIT_DISPATCH(TBE_NBS_LAUNCH, max_units);
+#undef TBE_NBS_LAUNCH
+#undef TBE_NBIT_DISPATCH
   return out;
 }
 

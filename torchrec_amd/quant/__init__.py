@@ -1,7 +1,10 @@
-"""Quantized (int8) inference modules (reference: torchrec/quant/__init__.py)."""
+"""Quantized (INT8/INT4/INT2) inference modules (reference: torchrec/quant/__init__.py)."""
 
 from torchrec_amd.quant.embedding_modules import (  # noqa: F401
     EmbeddingBagCollection,
     EmbeddingCollection,
     QuantTableBatchedEmbeddingBags,
+    dequantize_rowwise_nbit,
+    nbit_row_stride,
+    quantize_rowwise_nbit,
 )

@@ -1,13 +1,20 @@
-"""Quantized (int8 rowwise) inference embedding modules.
+"""Quantized (rowwise INT8 / INT4 / INT2) inference embedding modules.
 
 Reference parity: torchrec/quant/embedding_modules.py
 (quant EmbeddingBagCollection :346 with from_float / quantize_state_dict
-:217; EmbeddingCollection :748) — backed by the CDNA4 int8 TBE kernels
+:217; EmbeddingCollection :748) — backed by the CDNA4 quantized TBE kernels
 (ops/csrc/quant_tbe.hip) instead of FBGEMM IntNBit.
+
+Packed row, for bits in {8, 4, 2}: ``[codes: D*bits/8 B][fp16 scale]
+[fp16 bias][zero padding]``, stride rounded up to 16 B. Element ``e`` sits in
+byte ``e*bits // 8`` at bit ``(e*bits) % 8``, low bits first. ``w = q * scale
++ bias``. The width is a per-table choice (``EmbeddingBagConfig.data_type``);
+a module whose tables are all INT8 runs exactly the INT8 kernels.
 """
 
 from __future__ import annotations
 
+import dataclasses
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -15,6 +22,7 @@ import torch.nn as nn
 
 from torchrec_amd import ops
 from torchrec_amd.modules.embedding_configs import (
+    DATA_TYPE_NUM_BITS,
     DataType,
     EmbeddingBagConfig,
     EmbeddingConfig,
@@ -26,9 +34,38 @@ from torchrec_amd.modules.embedding_modules import (
 )
 from torchrec_amd.sparse.jagged_tensor import JaggedTensor, KeyedJaggedTensor, KeyedTensor
 
+_QUANT_DATA_TYPES = (DataType.INT8, DataType.INT4, DataType.INT2)
+# output columns one lane of the n-bit kernels owns, by width (quant_tbe.hip: CodeUnit)
+_LANE_COLS = {8: 4, 4: 8, 2: 8}
+
+
+def quant_data_type(data_type: object) -> DataType:
+    """The quantized width a table is served at: INT8/INT4/INT2 (given as a
+    DataType or its name) are honoured, anything else means INT8."""
+    for dt in _QUANT_DATA_TYPES:
+        if data_type is dt or data_type == dt.name:
+            return dt
+    return DataType.INT8
+
 
 def int8_row_stride(D: int) -> int:
     return ((D + 4 + 15) // 16) * 16
+
+
+def _check_nbit_dim(D: int, bits: int) -> None:
+    if bits not in (8, 4, 2):
+        raise ValueError(f"quantized rows are 8, 4 or 2 bits wide, got {bits}")
+    if D <= 0 or (D * bits) % 32 != 0:
+        raise ValueError(
+            f"embedding_dim {D} cannot be packed at {bits} bits: D*bits must be a "
+            f"multiple of 32 (D % {32 // bits} == 0)"
+        )
+
+
+def nbit_row_stride(D: int, bits: int) -> int:
+    """Bytes per packed row: codes + fp16 scale + fp16 bias, rounded up to 16."""
+    _check_nbit_dim(D, bits)
+    return ((D * bits // 8 + 4 + 15) // 16) * 16
 
 
 def quantize_rowwise_int8(weights: torch.Tensor) -> torch.Tensor:
@@ -60,9 +97,68 @@ def dequantize_rowwise_int8(packed: torch.Tensor, D: int) -> torch.Tensor:
     return q * scale.unsqueeze(1) + bias.unsqueeze(1)
 
 
+def quantize_rowwise_nbit(weights: torch.Tensor, bits: int) -> torch.Tensor:
+    """fp32 [R, D] -> packed ``bits``-wide rows [R, stride] (CPU ref / HIP kernel).
+
+    INT4/INT2 codes are taken against the STORED fp16 scale and bias, so an
+    interior value is off by at most half a stored step. ``bits == 8`` is the
+    INT8 quantiser, unchanged."""
+    R, D = weights.shape
+    stride = nbit_row_stride(D, bits)
+    if bits == 8:
+        return quantize_rowwise_int8(weights)
+    if weights.is_cuda:
+        ops.hip_ops()
+        return torch.ops.trec_amd.quantize_rowwise_nbit(weights, bits)
+    levels = (1 << bits) - 1
+    code_bytes = D * bits // 8
+    mn = weights.min(dim=1).values
+    mx = weights.max(dim=1).values
+    scale_h = ((mx - mn) / float(levels)).half()
+    bias_h = mn.half()
+    scale = scale_h.float().unsqueeze(1)
+    bias = bias_h.float().unsqueeze(1)
+    q = torch.floor((weights - bias) / scale + 0.5).clamp(0, levels)
+    q = torch.where(scale == 0, torch.zeros_like(q), q).to(torch.uint8)
+    per_byte = 8 // bits
+    shifts = torch.arange(per_byte, dtype=torch.uint8) * bits
+    codes = (q.reshape(R, code_bytes, per_byte) << shifts).sum(dim=2).to(torch.uint8)
+    out = torch.zeros(R, stride, dtype=torch.uint8)
+    out[:, :code_bytes] = codes
+    sb = torch.stack([scale_h, bias_h], dim=1)  # [R, 2] fp16
+    out[:, code_bytes : code_bytes + 4] = sb.view(torch.uint8).reshape(R, 4)
+    return out
+
+
+def unpack_codes_nbit(packed: torch.Tensor, D: int, bits: int) -> torch.Tensor:
+    """Packed rows -> the integer codes, uint8 [R, D]."""
+    _check_nbit_dim(D, bits)
+    R = packed.shape[0]
+    code_bytes = D * bits // 8
+    per_byte = 8 // bits
+    shifts = torch.arange(per_byte, dtype=torch.uint8, device=packed.device) * bits
+    codes = (packed[:, :code_bytes].unsqueeze(2) >> shifts) & ((1 << bits) - 1)
+    return codes.reshape(R, D)
+
+
+def dequantize_rowwise_nbit(packed: torch.Tensor, D: int, bits: int) -> torch.Tensor:
+    """Packed ``bits``-wide rows -> fp32 [R, D] using the stored fp16 scale/bias."""
+    R = packed.shape[0]
+    code_bytes = D * bits // 8
+    q = unpack_codes_nbit(packed, D, bits).float()
+    sb = packed[:, code_bytes : code_bytes + 4].reshape(R, 2, 2).view(torch.float16)
+    sb = sb.reshape(R, 2)
+    scale = sb[:, 0].float()
+    bias = sb[:, 1].float()
+    return q * scale.unsqueeze(1) + bias.unsqueeze(1)
+
+
 class QuantTableBatchedEmbeddingBags(nn.Module):
-    """Inference-only int8 TBE (pooled). Flat packed buffer, per-table byte
-    offsets; GPU path = tbe_forward_pooled_int8, CPU path = dequant reference."""
+    """Inference-only quantized TBE (pooled). Flat packed buffer, per-table byte
+    offsets and per-table width (``weight_dtypes``: INT8/INT4/INT2, None = all
+    INT8). GPU path = tbe_forward_pooled_int8 when every table is INT8, else
+    tbe_forward_pooled_nbit (one launch for mixed widths); CPU path = dequant
+    reference."""
 
     def __init__(
         self,
@@ -71,6 +167,7 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         pooling: PoolingType = PoolingType.SUM,
         device: Optional[torch.device] = None,
         location: str = "device",  # "device" (HBM) | "managed" (pinned host, QUANT_UVM)
+        weight_dtypes: Optional[List[DataType]] = None,
     ) -> None:
         super().__init__()
         device = device or torch.device("cpu")
@@ -78,13 +175,29 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         qdevice = torch.device("cpu") if self._uvm else device
         self._specs = specs
         T = len(specs)
+        if weight_dtypes is None:
+            weight_dtypes = [DataType.INT8] * T
+        if len(weight_dtypes) != T:
+            raise ValueError(f"weight_dtypes has {len(weight_dtypes)} entries for {T} tables")
+        for dt in weight_dtypes:
+            if dt not in _QUANT_DATA_TYPES:
+                raise ValueError(f"quantized tables are INT8, INT4 or INT2, got {dt}")
+        self._weight_dtypes = list(weight_dtypes)
+        self._bits = [DATA_TYPE_NUM_BITS[dt] for dt in weight_dtypes]
+        self._all_int8 = all(b == 8 for b in self._bits)
+        if not self._all_int8:
+            for (name, _, dim), b in zip(specs, self._bits):
+                try:
+                    _check_nbit_dim(dim, b)
+                except ValueError as e:
+                    raise ValueError(f"table {name}: {e}") from None
         self._feature_table_map = feature_table_map or list(range(T))
         F = len(self._feature_table_map)
         self._num_features = F
         self.pooling = pooling
         byte_offsets = [0]
-        for (_, rows, dim) in specs:
-            byte_offsets.append(byte_offsets[-1] + rows * int8_row_stride(dim))
+        for (_, rows, dim), b in zip(specs, self._bits):
+            byte_offsets.append(byte_offsets[-1] + rows * self._stride(dim, b))
         dims = [s[2] for s in specs]
         feat_dims = [dims[t] for t in self._feature_table_map]
         d_out = [0]
@@ -92,6 +205,11 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
             d_out.append(d_out[-1] + d)
         self._total_D = d_out[-1]
         self._max_D = max(dims) if dims else 0
+        # widest row in lane units, what the n-bit launch is sized by: a lane
+        # owns 4 columns of an INT8 row and 8 of an INT4 or INT2 row
+        self._max_units = max(
+            (d // _LANE_COLS[b] for d, b in zip(dims, self._bits)), default=0
+        )
         qw = torch.zeros(byte_offsets[-1], dtype=torch.uint8, device=qdevice)
         if getattr(self, "_uvm", False):
             qw = qw.pin_memory()
@@ -99,22 +217,39 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         reg = lambda n, t: self.register_buffer(n, t.to(device), persistent=False)
         reg("_table_byte_offsets", torch.tensor(byte_offsets[:-1], dtype=torch.int64))
         reg("_dims_t", torch.tensor(dims, dtype=torch.int32))
+        reg("_weight_bits_t", torch.tensor(self._bits, dtype=torch.int32))
         reg("_feat_table_t", torch.tensor(self._feature_table_map, dtype=torch.int32))
         reg("_d_out_offsets", torch.tensor(d_out, dtype=torch.int64))
         reg("_empty_f", torch.empty(0, dtype=torch.float32))
 
+    @staticmethod
+    def _stride(dim: int, bits: int) -> int:
+        # INT8 keeps its own stride rule (no dim check: CPU lookups of odd
+        # dims keep working as before)
+        return int8_row_stride(dim) if bits == 8 else nbit_row_stride(dim, bits)
+
     def load_float_table(self, i: int, weights: torch.Tensor) -> None:
         name, rows, dim = self._specs[i]
-        packed = quantize_rowwise_int8(weights.to(self.qweights.device).float())
+        w = weights.to(self.qweights.device).float()
+        if self._bits[i] == 8:
+            packed = quantize_rowwise_int8(w)
+        else:
+            packed = quantize_rowwise_nbit(w, self._bits[i])
         start = int(self._table_byte_offsets[i])
         self.qweights[start : start + packed.numel()].copy_(packed.reshape(-1))
 
     def packed_table(self, i: int) -> torch.Tensor:
         name, rows, dim = self._specs[i]
         start = int(self._table_byte_offsets[i])
-        return self.qweights[start : start + rows * int8_row_stride(dim)].view(
-            rows, int8_row_stride(dim)
-        )
+        stride = self._stride(dim, self._bits[i])
+        return self.qweights[start : start + rows * stride].view(rows, stride)
+
+    def dequantized_table(self, i: int) -> torch.Tensor:
+        """fp32 [rows, dim] of table ``i`` from its packed bytes."""
+        name, rows, dim = self._specs[i]
+        if self._bits[i] == 8:
+            return dequantize_rowwise_int8(self.packed_table(i), dim)
+        return dequantize_rowwise_nbit(self.packed_table(i), dim, self._bits[i])
 
     @torch.no_grad()
     def forward(
@@ -126,6 +261,22 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         B = (offsets.numel() - 1) // self._num_features
         if self.qweights.is_cuda or (self.qweights.is_pinned() and indices.is_cuda):
             ops.hip_ops()
+            if not self._all_int8:
+                return torch.ops.trec_amd.tbe_forward_pooled_nbit(
+                    self.qweights,
+                    self._table_byte_offsets,
+                    self._dims_t,
+                    self._weight_bits_t,
+                    self._feat_table_t,
+                    self._d_out_offsets,
+                    indices,
+                    offsets,
+                    per_sample_weights if per_sample_weights is not None else self._empty_f,
+                    B,
+                    self._total_D,
+                    self._max_units,
+                    self.pooling == PoolingType.MEAN,
+                )
             return torch.ops.trec_amd.tbe_forward_pooled_int8(
                 self.qweights,
                 self._table_byte_offsets,
@@ -143,8 +294,7 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         # CPU reference
         outs = []
         for f, t in enumerate(self._feature_table_map):
-            name, rows, dim = self._specs[t]
-            w = dequantize_rowwise_int8(self.packed_table(t), dim)
+            w = self.dequantized_table(t)
             off = offsets[f * B : (f + 1) * B + 1] - offsets[f * B]
             idx = indices[int(offsets[f * B]) : int(offsets[(f + 1) * B])]
             pw = (
@@ -164,9 +314,51 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
             )
         return torch.cat(outs, dim=1)
 
+    @torch.no_grad()
+    def forward_sequence(
+        self, indices: torch.Tensor, feat_val_offsets: torch.Tensor, dim: int
+    ) -> torch.Tensor:
+        """GPU per-row lookup [N, dim]: tbe_forward_seq_int8 when every table is
+        INT8, else tbe_forward_seq_nbit. ``feat_val_offsets`` is [F+1]."""
+        ops.hip_ops()
+        if not self._all_int8:
+            return torch.ops.trec_amd.tbe_forward_seq_nbit(
+                self.qweights,
+                self._table_byte_offsets,
+                self._dims_t,
+                self._weight_bits_t,
+                self._feat_table_t,
+                feat_val_offsets,
+                indices,
+                dim,
+                self._max_units,
+            )
+        return torch.ops.trec_amd.tbe_forward_seq_int8(
+            self.qweights,
+            self._table_byte_offsets,
+            self._dims_t,
+            self._feat_table_t,
+            feat_val_offsets,
+            indices,
+            dim,
+            self._max_D,
+        )
+
+
+def _resolve_weight_dtype(
+    name: str,
+    weight_dtype: DataType,
+    per_table_weight_dtype: Optional[Dict[str, DataType]],
+) -> DataType:
+    dt = (per_table_weight_dtype or {}).get(name, weight_dtype)
+    if dt not in _QUANT_DATA_TYPES:
+        raise ValueError(f"table {name}: quantized tables are INT8, INT4 or INT2, got {dt}")
+    return dt
+
 
 class EmbeddingBagCollection(nn.Module):
-    """Quantized EBC (reference quant/embedding_modules.py:346)."""
+    """Quantized EBC (reference quant/embedding_modules.py:346). Each table is
+    served at its config's ``data_type`` when that is INT8/INT4/INT2, else INT8."""
 
     def __init__(
         self,
@@ -187,10 +379,17 @@ class EmbeddingBagCollection(nn.Module):
             feature_table_map=[i for i, t in enumerate(tables) for _ in t.feature_names],
             pooling=next(iter(poolings)) if poolings else PoolingType.SUM,
             device=device,
+            weight_dtypes=[quant_data_type(t.data_type) for t in tables],
         )
 
     @classmethod
-    def from_float(cls, module: FloatEBC, output_dtype: torch.dtype = torch.float32):
+    def from_float(
+        cls,
+        module: FloatEBC,
+        output_dtype: torch.dtype = torch.float32,
+        weight_dtype: DataType = DataType.INT8,
+        per_table_weight_dtype: Optional[Dict[str, DataType]] = None,
+    ):
         tables = module.embedding_bag_configs()
         device = next(module.parameters()).device if any(True for _ in module.parameters()) else torch.device("cpu")
         q = cls(
@@ -201,7 +400,9 @@ class EmbeddingBagCollection(nn.Module):
                     name=t.name,
                     feature_names=list(t.feature_names),
                     pooling=t.pooling,
-                    data_type=DataType.INT8,
+                    data_type=_resolve_weight_dtype(
+                        t.name, weight_dtype, per_table_weight_dtype
+                    ),
                 )
                 for t in tables
             ],
@@ -235,7 +436,9 @@ class EmbeddingBagCollection(nn.Module):
 
 
 class EmbeddingCollection(nn.Module):
-    """Quantized sequence EC (reference quant/embedding_modules.py:748)."""
+    """Quantized sequence EC (reference quant/embedding_modules.py:748). Each
+    table is served at its config's ``data_type`` when that is INT8/INT4/INT2,
+    else INT8."""
 
     def __init__(
         self,
@@ -253,11 +456,25 @@ class EmbeddingCollection(nn.Module):
             [(t.name, t.num_embeddings, t.embedding_dim) for t in tables],
             feature_table_map=[i for i, t in enumerate(tables) for _ in t.feature_names],
             device=device,
+            weight_dtypes=[quant_data_type(t.data_type) for t in tables],
         )
 
     @classmethod
-    def from_float(cls, module: FloatEC, output_dtype: torch.dtype = torch.float32):
-        tables = module.embedding_configs()
+    def from_float(
+        cls,
+        module: FloatEC,
+        output_dtype: torch.dtype = torch.float32,
+        weight_dtype: DataType = DataType.INT8,
+        per_table_weight_dtype: Optional[Dict[str, DataType]] = None,
+    ):
+        tables = [
+            dataclasses.replace(
+                t,
+                feature_names=list(t.feature_names),
+                data_type=_resolve_weight_dtype(t.name, weight_dtype, per_table_weight_dtype),
+            )
+            for t in module.embedding_configs()
+        ]
         q = cls(tables=tables)
         for i, t in enumerate(tables):
             q._tbe.load_float_table(i, module.embeddings[t.name].weight.detach())
@@ -278,23 +495,12 @@ class EmbeddingCollection(nn.Module):
         if tbe.qweights.is_cuda or (
             tbe.qweights.is_pinned() and features.values().is_cuda
         ):
-            ops.hip_ops()
             feat_val_offsets = offsets[:: B][: F + 1].contiguous()
-            rows = torch.ops.trec_amd.tbe_forward_seq_int8(
-                tbe.qweights,
-                tbe._table_byte_offsets,
-                tbe._dims_t,
-                tbe._feat_table_t,
-                feat_val_offsets,
-                features.values(),
-                self._dim,
-                tbe._max_D,
-            )
+            rows = tbe.forward_sequence(features.values(), feat_val_offsets, self._dim)
         else:
             rows_l = []
             for f, t in enumerate(tbe._feature_table_map):
-                name, r, dim = tbe._specs[t]
-                w = dequantize_rowwise_int8(tbe.packed_table(t), dim)
+                w = tbe.dequantized_table(t)
                 idx = features.values()[int(offsets[f * B]) : int(offsets[(f + 1) * B])]
                 rows_l.append(w[idx])
             rows = torch.cat(rows_l, dim=0) if rows_l else torch.empty(0, self._dim)
