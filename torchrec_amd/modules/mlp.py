@@ -49,14 +49,23 @@ def _use_splitk() -> bool:
     return os.environ.get("TREC_SPLITK_WGRAD", "1") == "1"
 
 
-def _splitk_wgrad(g: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
-    """dW = g^T @ x with K = batch split across a bmm (split-K that
+def _splitk_ok(B: int) -> bool:
+    return _use_splitk() and B >= 4096 and B % 8 == 0
+
+
+def _splitk_parts(g: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """The 8 [N, K] split-K chunks of g^T @ x as one bmm (split-K that
     hipBLASLt's heuristic refuses to pick for TN deep-K shapes)."""
     B = g.shape[0]
-    if _use_splitk() and B >= 4096 and B % 8 == 0:
-        gv = g.view(8, B // 8, g.shape[1])
-        xv = x.view(8, B // 8, x.shape[1])
-        return torch.bmm(gv.transpose(1, 2), xv).sum(0)
+    gv = g.view(8, B // 8, g.shape[1])
+    xv = x.view(8, B // 8, x.shape[1])
+    return torch.bmm(gv.transpose(1, 2), xv)
+
+
+def _splitk_wgrad(g: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """dW = g^T @ x with K = batch split across a bmm when it pays."""
+    if _splitk_ok(g.shape[0]):
+        return _splitk_parts(g, x).sum(0)
     return g.t() @ x
 
 
@@ -102,11 +111,23 @@ class _LinearReLUFused(torch.autograd.Function):
             dx = g @ w if ctx.needs_input_grad[0] else None
             dw, db = torch.ops.trec_amd.lt_wgrad_bgrad(g, x)
             return dx, dw, db
-        # relu_bwd_col_sum kernel: opt-in — the scalar-load version measured
-        # SLOWER than torch's vectorized threshold-backward + reduce pair in
-        # the full step (1.88 vs 1.39 ms/step A/B); split-K wgrad is the win
+        # fused relu-mask + bias-grad kernels (16 B vector loads, block-
+        # cooperative fp32 partials): opt-in. The hipGraph-captured bench,
+        # which is GPU-time-bound, turns them on; the launch-bound eager
+        # pipeline keeps torch's threshold-backward + reduce pair.
         if os.environ.get("TREC_RELU_COLSUM", "0") == "1":
             ops.hip_ops()
+            if _splitk_ok(dy.shape[0]):
+                # two kernels around the GEMMs: mask + [G, N] partials, then
+                # one launch that sums the split-K chunks and folds db
+                g, partial = torch.ops.trec_amd.relu_bwd_colsum_partial(
+                    dy.contiguous(), y
+                )
+                dx = g @ w if ctx.needs_input_grad[0] else None
+                dw, db = torch.ops.trec_amd.splitk_fold_bias(
+                    _splitk_parts(g, x), partial
+                )
+                return dx, dw, db.to(w.dtype)
             g, db = torch.ops.trec_amd.relu_bwd_col_sum(dy.contiguous(), y)
             db = db.to(w.dtype)
         else:

@@ -136,6 +136,10 @@ at::Tensor bce_with_logits_bwd(const at::Tensor& logits, const at::Tensor& label
                                const at::Tensor& grad_out);
 std::tuple<at::Tensor, at::Tensor> relu_bwd_col_sum(const at::Tensor& grad_out,
                                                     const at::Tensor& y);
+std::tuple<at::Tensor, at::Tensor> relu_bwd_colsum_partial(const at::Tensor& grad_out,
+                                                           const at::Tensor& y);
+std::tuple<at::Tensor, at::Tensor> splitk_fold_bias(const at::Tensor& parts,
+                                                    const at::Tensor& partial);
 // interaction_mfma.hip
 at::Tensor interaction_mfma_forward(const at::Tensor& dense, const at::Tensor& sparse,
                                     const at::Tensor& pi, const at::Tensor& pj);
@@ -250,6 +254,8 @@ TORCH_LIBRARY(trec_amd, m) {
   m.def("col_sum(Tensor input) -> Tensor");
   m.def("interaction_forward(Tensor dense, Tensor sparse, Tensor pi, Tensor pj) -> Tensor");
   m.def("relu_bwd_col_sum(Tensor grad_out, Tensor y) -> (Tensor, Tensor)");
+  m.def("relu_bwd_colsum_partial(Tensor grad_out, Tensor y) -> (Tensor g, Tensor partial)");
+  m.def("splitk_fold_bias(Tensor parts, Tensor partial) -> (Tensor dW, Tensor db)");
   m.def("lt_linear_relu_fwd(Tensor x, Tensor w, Tensor b) -> Tensor");
   m.def("lt_wgrad_bgrad(Tensor g, Tensor x) -> (Tensor, Tensor)");
   m.def("relu_bwd_mask(Tensor grad_out, Tensor y) -> Tensor");
@@ -300,6 +306,8 @@ TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
   m.impl("col_sum", trec_amd::col_sum);
   m.impl("interaction_forward", trec_amd::interaction_forward);
   m.impl("relu_bwd_col_sum", trec_amd::relu_bwd_col_sum);
+  m.impl("relu_bwd_colsum_partial", trec_amd::relu_bwd_colsum_partial);
+  m.impl("splitk_fold_bias", trec_amd::splitk_fold_bias);
   m.impl("lt_linear_relu_fwd", trec_amd::lt_linear_relu_fwd);
   m.impl("lt_wgrad_bgrad", trec_amd::lt_wgrad_bgrad);
   m.impl("relu_bwd_mask", trec_amd::relu_bwd_mask);

@@ -1,16 +1,22 @@
 // Fused MLP backward helpers for MI355X (gfx950).
 //
-// relu_bwd_col_sum: one pass over dY producing BOTH the relu-masked gradient
-// g = dY * (y > 0) and the bias gradient db = colsum(g) (fp32 accumulate,
-// deterministic two-phase fixed-partition reduction). Replaces torch's
-// separate compare + mul + column reduce (three dY-sized passes) with one.
-// 16-bit dtypes move as 8-element (16 B) vectors per lane (Guideline 13:
-// scalar bf16 loads are ~2.5x slower).
+// relu_bwd_colsum_partial: one pass over dY producing BOTH the relu-masked
+// gradient g = dY * (y > 0) and a small fp32 [G, N] table of bias-gradient
+// partials (block-cooperative: 8 column lanes x 32 row lanes, LDS fold, one
+// partial row per block, G*N*4 B <= 256 KB). Replaces torch's separate
+// compare + mul + column reduce (three dY-sized passes) with one. 16-bit
+// dtypes move as 8-element (16 B) vectors per lane (Guideline 13: scalar
+// bf16 loads are ~2.5x slower).
+// splitk_fold_bias: sums the S split-K wgrad chunks AND folds the partial
+// table into db in one launch (trailing blocks), so a ReLU layer's backward
+// tail is two kernels. relu_bwd_col_sum (non-split path) = partial kernel +
+// one cast-fused final fold. All reduction orders are fixed: bitwise
+// repeatable, no atomics, no counters.
 
 #include <torch/extension.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
-#include <cstdlib>
+#include <cstdint>
 #include <type_traits>
 
 #include "common.h"
@@ -21,171 +27,259 @@ static inline hipStream_t mlp_stream() {
   return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
 }
 
-// VPT elements per thread along the column axis; rows_per_group rows per
-// partial. Work item = (column 8-chunk, row group), grid-strided.
-template <typename scalar_t, int VPT>
+// ---------------------------------------------------------------------------
+// relu mask + bias-grad partials. A 256-thread block owns a column tile of
+// kColLanes * VPT columns and a contiguous group of rows; thread (rl, cl)
+// owns one 16 B column vector and visits rows rl, rl + 32, ... of the group,
+// kRowUnroll rows of loads in flight. A wave covers 8 rows x 128 B.
+// ---------------------------------------------------------------------------
+constexpr int kColLanes = 8;
+constexpr int kRowLanes = kBlockThreads / kColLanes;  // 32
+constexpr int kRowUnroll = 4;
+constexpr int kMaxGroups = 256;                  // blockIdx.y range, fold depth
+constexpr int64_t kPartialElems = 256 * 1024 / 4;  // G * N <= 64 Ki floats
+
+template <typename scalar_t, int VPT, bool VEC>
 __global__ void __launch_bounds__(kBlockThreads) relu_bwd_colsum_partial_kernel(
     const scalar_t* __restrict__ dy, const scalar_t* __restrict__ y, int64_t M,
-    int64_t N, int rows_per_group, int n_groups, scalar_t* __restrict__ g,
-    float* __restrict__ partial /* [G, N] */, int* __restrict__ counters,
-    int n_tiles) {
-  // zero the finish kernel's per-tile semaphores (it launches after us on
-  // the same stream, so ordering is guaranteed)
-  if (counters && blockIdx.x == 0)
-    for (int t = threadIdx.x; t < n_tiles; t += blockDim.x) counters[t] = 0;
-  const int64_t col_chunks = (N + VPT - 1) / VPT;
-  const int64_t items = col_chunks * n_groups;
-  for (int64_t it = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-       it < items; it += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    const int grp = static_cast<int>(it / col_chunks);
-    const int64_t c0 = (it - static_cast<int64_t>(grp) * col_chunks) * VPT;
-    const int64_t r0 = static_cast<int64_t>(grp) * rows_per_group;
-    const int64_t r1 = min(M, r0 + static_cast<int64_t>(rows_per_group));
-    float acc[VPT];
+    int64_t N, int64_t rows_per_group, scalar_t* __restrict__ g,
+    float* __restrict__ partial /* [gridDim.y, N] */) {
+  constexpr int TILE_N = kColLanes * VPT;
+  __shared__ float red[kRowLanes][TILE_N];
+  const int cl = threadIdx.x % kColLanes;
+  const int rl = threadIdx.x / kColLanes;
+  const int64_t c0 = static_cast<int64_t>(blockIdx.x) * TILE_N + cl * VPT;
+  const int64_t r0 = static_cast<int64_t>(blockIdx.y) * rows_per_group;
+  const int64_t r1 = min(M, r0 + rows_per_group);
+  float acc[VPT];
 #pragma unroll
-    for (int v = 0; v < VPT; ++v) acc[v] = 0.f;
-    const bool full = (c0 + VPT <= N);
-    for (int64_t r = r0; r < r1; ++r) {
-      const int64_t base = r * N + c0;
-      if (full && sizeof(scalar_t) == 2 && VPT == 8) {
-        // 8 x 16-bit = one 16 B load per operand, one 16 B store
-        uint4 qy = *reinterpret_cast<const uint4*>(y + base);
-        uint4 qd = *reinterpret_cast<const uint4*>(dy + base);
-        const scalar_t* py = reinterpret_cast<const scalar_t*>(&qy);
-        const scalar_t* pd = reinterpret_cast<const scalar_t*>(&qd);
-        uint4 qo;
-        scalar_t* po = reinterpret_cast<scalar_t*>(&qo);
+  for (int v = 0; v < VPT; ++v) acc[v] = 0.f;
+  if (c0 < N) {
+    if constexpr (VEC) {
+      // N % VPT == 0 and 16 B-aligned bases: every chunk is whole and aligned
+      for (int64_t r = r0 + rl; r < r1; r += kRowLanes * kRowUnroll) {
+        uint4 qy[kRowUnroll], qd[kRowUnroll];
+#pragma unroll
+        for (int u = 0; u < kRowUnroll; ++u) {
+          const int64_t rr = r + u * kRowLanes;
+          qy[u] = make_uint4(0, 0, 0, 0);
+          qd[u] = make_uint4(0, 0, 0, 0);
+          if (rr < r1) {
+            qy[u] = *reinterpret_cast<const uint4*>(y + rr * N + c0);
+            qd[u] = *reinterpret_cast<const uint4*>(dy + rr * N + c0);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kRowUnroll; ++u) {
+          const int64_t rr = r + u * kRowLanes;
+          if (rr < r1) {
+            const scalar_t* py = reinterpret_cast<const scalar_t*>(&qy[u]);
+            const scalar_t* pd = reinterpret_cast<const scalar_t*>(&qd[u]);
+            uint4 qo;
+            scalar_t* po = reinterpret_cast<scalar_t*>(&qo);
+#pragma unroll
+            for (int v = 0; v < VPT; ++v) {
+              float gv = (emb2float(py[v]) > 0.f) ? emb2float(pd[v]) : 0.f;
+              po[v] = float2emb(gv, scalar_t{});
+              acc[v] += gv;
+            }
+            *reinterpret_cast<uint4*>(g + rr * N + c0) = qo;
+          }
+        }
+      }
+    } else {
+      // scalar tail path: N % VPT != 0 (row bases lose 16 B alignment)
+      for (int64_t r = r0 + rl; r < r1; r += kRowLanes) {
+        const int64_t base = r * N + c0;
 #pragma unroll
         for (int v = 0; v < VPT; ++v) {
-          float gv = (emb2float(py[v]) > 0.f) ? emb2float(pd[v]) : 0.f;
-          po[v] = float2emb(gv, scalar_t{});
-          acc[v] += gv;
-        }
-        *reinterpret_cast<uint4*>(g + base) = qo;
-      } else if (full && sizeof(scalar_t) == 4 && VPT == 4) {
-        uint4 qy = *reinterpret_cast<const uint4*>(y + base);
-        uint4 qd = *reinterpret_cast<const uint4*>(dy + base);
-        const scalar_t* py = reinterpret_cast<const scalar_t*>(&qy);
-        const scalar_t* pd = reinterpret_cast<const scalar_t*>(&qd);
-        uint4 qo;
-        scalar_t* po = reinterpret_cast<scalar_t*>(&qo);
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) {
-          float gv = (emb2float(py[v]) > 0.f) ? emb2float(pd[v]) : 0.f;
-          po[v] = float2emb(gv, scalar_t{});
-          acc[v] += gv;
-        }
-        *reinterpret_cast<uint4*>(g + base) = qo;
-      } else {
-        for (int v = 0; v < VPT && c0 + v < N; ++v) {
-          float gv = (emb2float(y[base + v]) > 0.f) ? emb2float(dy[base + v]) : 0.f;
-          g[base + v] = float2emb(gv, scalar_t{});
-          acc[v] += gv;
+          if (c0 + v < N) {
+            float gv = (emb2float(y[base + v]) > 0.f) ? emb2float(dy[base + v]) : 0.f;
+            g[base + v] = float2emb(gv, scalar_t{});
+            acc[v] += gv;
+          }
         }
       }
     }
-    float* prow = partial + static_cast<int64_t>(grp) * N + c0;
+  }
 #pragma unroll
-    for (int v = 0; v < VPT; ++v)
-      if (c0 + v < N) prow[v] = acc[v];
+  for (int v = 0; v < VPT; ++v) red[rl][cl * VPT + v] = acc[v];
+  __syncthreads();
+  // fixed-order fold of the 32 row lanes: one partial row per block
+  if (threadIdx.x < TILE_N) {
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * TILE_N + threadIdx.x;
+    if (c < N) {
+      float s = 0.f;
+#pragma unroll
+      for (int k = 0; k < kRowLanes; ++k) s += red[k][threadIdx.x];
+      partial[static_cast<int64_t>(blockIdx.y) * N + c] = s;
+    }
   }
 }
 
-// one-kernel segment+final fold, take 2 (first try rejected at 21.8 us for
-// per-element ORDERED atomics): phase 1 writes per-segment sums with plain
-// float4 stores; publication is one device fence + a RELAXED counter; the
-// last block per column tile re-fences and folds the 32 segment rows with
-// PLAIN float4 loads (independent, pipelined). Fold order is fixed =>
-// deterministic.
+// Fold one 16-column tile of the [G, N] partial table into db: 16 row lanes
+// each sum rows rl, rl + 16, ... in ascending order, then lane 0 folds the 16
+// lane sums through LDS in ascending order. Whole block must call this.
+constexpr int kFoldCols = 16;
+constexpr int kFoldRows = kBlockThreads / kFoldCols;  // 16
+
 template <typename o_t>
-__global__ void __launch_bounds__(kBlockThreads) colsum_finish2_kernel(
-    const float* __restrict__ partial, int G, int seg_rows, int64_t N,
-    float* __restrict__ seg /* [S, N] */, int* __restrict__ counters,
-    int S, o_t* __restrict__ db) {
-  // each thread owns 4 consecutive columns (float4 lanes)
-  int64_t c4 = (static_cast<int64_t>(blockIdx.x) * kBlockThreads + threadIdx.x) * 4;
-  int sgm = blockIdx.y;
-  if (c4 + 4 <= N) {
-    int g0 = sgm * seg_rows;
-    int g1 = min(G, g0 + seg_rows);
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int grp = g0; grp < g1; ++grp) {
-      float4 v = *reinterpret_cast<const float4*>(
-          partial + static_cast<int64_t>(grp) * N + c4);
-      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-    *reinterpret_cast<float4*>(seg + static_cast<int64_t>(sgm) * N + c4) = acc;
-  } else {
-    for (int64_t c = c4; c < N; ++c) {
-      int g0 = sgm * seg_rows, g1 = min(G, g0 + seg_rows);
-      float a = 0.f;
-      for (int grp = g0; grp < g1; ++grp)
-        a += partial[static_cast<int64_t>(grp) * N + c];
-      seg[static_cast<int64_t>(sgm) * N + c] = a;
-    }
-  }
-  __threadfence();
-  __syncthreads();
-  __shared__ int last;
-  if (threadIdx.x == 0)
-    last = (__hip_atomic_fetch_add(&counters[blockIdx.x], 1, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT) == S - 1);
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
-  if (c4 + 4 <= N) {
-    float4 tot = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int ss = 0; ss < S; ++ss) {
-      float4 v = *reinterpret_cast<const float4*>(
-          seg + static_cast<int64_t>(ss) * N + c4);
-      tot.x += v.x; tot.y += v.y; tot.z += v.z; tot.w += v.w;
-    }
-    db[c4 + 0] = float2emb(tot.x, o_t{});
-    db[c4 + 1] = float2emb(tot.y, o_t{});
-    db[c4 + 2] = float2emb(tot.z, o_t{});
-    db[c4 + 3] = float2emb(tot.w, o_t{});
-  } else {
-    for (int64_t c = c4; c < N; ++c) {
-      float tot = 0.f;
-      for (int ss = 0; ss < S; ++ss)
-        tot += seg[static_cast<int64_t>(ss) * N + c];
-      db[c] = float2emb(tot, o_t{});
-    }
-  }
-}
-
-// level-1 segment reduce: 2-D grid ((column tile) x S) collapses G rows to
-// S per-tile sums. Measured better than a single-kernel semaphore finish
-// (21.8 us) as a pair with the cast-fused final (9 + 8.5 us): the last-block
-// fold's 32-row tail ran on too few blocks.
-__global__ void __launch_bounds__(kBlockThreads) colsum_seg_f32_kernel(
-    const float* __restrict__ partial, int G, int seg_rows, int64_t N,
-    float* __restrict__ seg_out /* [S, N] */) {
-  int64_t c = static_cast<int64_t>(blockIdx.x) * kBlockThreads + threadIdx.x;
-  if (c >= N) return;
-  int s = blockIdx.y;
-  int g0 = s * seg_rows;
-  int g1 = min(G, g0 + seg_rows);
+__device__ __forceinline__ void fold_partial_tile(
+    const float* __restrict__ partial, int G, int64_t N, int64_t tile,
+    o_t* __restrict__ db, float (*red)[kFoldCols]) {
+  const int cl = threadIdx.x % kFoldCols;
+  const int rl = threadIdx.x / kFoldCols;
+  const int64_t c = tile * kFoldCols + cl;
   float acc = 0.f;
-  for (int grp = g0; grp < g1; ++grp)
-    acc += partial[static_cast<int64_t>(grp) * N + c];
-  seg_out[static_cast<int64_t>(s) * N + c] = acc;
+  if (c < N) {
+#pragma unroll 4
+    for (int grp = rl; grp < G; grp += kFoldRows)
+      acc += partial[static_cast<int64_t>(grp) * N + c];
+  }
+  red[rl][cl] = acc;
+  __syncthreads();
+  if (rl == 0 && c < N) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < kFoldRows; ++k) s += red[k][cl];
+    db[c] = float2emb(s, o_t{});
+  }
 }
 
 template <typename o_t>
 __global__ void __launch_bounds__(kBlockThreads) colsum_final_cast_kernel(
     const float* __restrict__ partial, int G, int64_t N, o_t* __restrict__ out) {
-  int64_t c = static_cast<int64_t>(blockIdx.x) * kBlockThreads + threadIdx.x;
-  if (c >= N) return;
-  float acc = 0.f;
-  for (int grp = 0; grp < G; ++grp) acc += partial[static_cast<int64_t>(grp) * N + c];
-  out[c] = float2emb(acc, o_t{});
+  __shared__ float red[kFoldRows][kFoldCols];
+  fold_partial_tile<o_t>(partial, G, N, blockIdx.x, out, red);
+}
+
+// Split-K chunk sum + bias-grad fold in one launch. Blocks [0, sum_blocks)
+// sum the S chunks of parts [S, E] elementwise (fp32 accumulate in chunk
+// order, one rounding); blocks [sum_blocks, gridDim.x) each fold one column
+// tile of partial [G, N] into db.
+constexpr int kChunkUnroll = 8;
+
+template <typename scalar_t, int VPT, bool VEC>
+__global__ void __launch_bounds__(kBlockThreads) splitk_fold_bias_kernel(
+    const scalar_t* __restrict__ parts, int S, int64_t E,
+    scalar_t* __restrict__ dw, int sum_blocks, const float* __restrict__ partial,
+    int G, int64_t N, scalar_t* __restrict__ db) {
+  __shared__ float red[kFoldRows][kFoldCols];
+  if (static_cast<int>(blockIdx.x) >= sum_blocks) {
+    fold_partial_tile<scalar_t>(partial, G, N, blockIdx.x - sum_blocks, db, red);
+    return;
+  }
+  const int64_t chunks = (E + VPT - 1) / VPT;
+  for (int64_t it = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+       it < chunks; it += static_cast<int64_t>(sum_blocks) * blockDim.x) {
+    const int64_t base = it * VPT;
+    float acc[VPT];
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) acc[v] = 0.f;
+    if constexpr (VEC) {
+      // E % VPT == 0 and 16 B-aligned bases
+      for (int s0 = 0; s0 < S; s0 += kChunkUnroll) {
+        uint4 q[kChunkUnroll];
+#pragma unroll
+        for (int u = 0; u < kChunkUnroll; ++u) {
+          q[u] = make_uint4(0, 0, 0, 0);
+          if (s0 + u < S)
+            q[u] = *reinterpret_cast<const uint4*>(
+                parts + static_cast<int64_t>(s0 + u) * E + base);
+        }
+#pragma unroll
+        for (int u = 0; u < kChunkUnroll; ++u) {
+          if (s0 + u < S) {
+            const scalar_t* p = reinterpret_cast<const scalar_t*>(&q[u]);
+#pragma unroll
+            for (int v = 0; v < VPT; ++v) acc[v] += emb2float(p[v]);
+          }
+        }
+      }
+      uint4 qo;
+      scalar_t* po = reinterpret_cast<scalar_t*>(&qo);
+#pragma unroll
+      for (int v = 0; v < VPT; ++v) po[v] = float2emb(acc[v], scalar_t{});
+      *reinterpret_cast<uint4*>(dw + base) = qo;
+    } else {
+      for (int s = 0; s < S; ++s) {
+#pragma unroll
+        for (int v = 0; v < VPT; ++v)
+          if (base + v < E) acc[v] += emb2float(parts[static_cast<int64_t>(s) * E + base + v]);
+      }
+#pragma unroll
+      for (int v = 0; v < VPT; ++v)
+        if (base + v < E) dw[base + v] = float2emb(acc[v], scalar_t{});
+    }
+  }
+}
+
+static inline bool aligned16(const void* p) {
+  return reinterpret_cast<uintptr_t>(p) % 16 == 0;
+}
+
+// launches the partial kernel; dy / yc / g contiguous [M, N], M, N > 0.
+// Returns partial [G, N] fp32 with G = min(256, 64Ki / N, row tiles).
+static at::Tensor launch_relu_bwd_partial(const at::Tensor& dy, const at::Tensor& yc,
+                                          at::Tensor& g) {
+  const int64_t M = dy.size(0), N = dy.size(1);
+  const int64_t row_tiles = (M + kRowLanes - 1) / kRowLanes;
+  int64_t G = std::min<int64_t>(kMaxGroups, std::max<int64_t>(1, kPartialElems / N));
+  G = std::max<int64_t>(1, std::min(G, row_tiles));
+  // whole row tiles per group, then drop groups left empty by the rounding
+  const int64_t rows_per_group = (row_tiles + G - 1) / G * kRowLanes;
+  G = (M + rows_per_group - 1) / rows_per_group;
+  auto partial = at::empty({G, N}, dy.options().dtype(at::kFloat));
+  auto stream = mlp_stream();
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::kHalf, at::kBFloat16, dy.scalar_type(),
+                                  "relu_bwd_colsum_partial", [&] {
+    if constexpr (std::is_same_v<scalar_t, double>) {
+      TORCH_CHECK(false, "fp64 unsupported");
+    } else {
+      using dev_t = typename DevType<scalar_t>::type;
+      constexpr int VPT = 16 / sizeof(dev_t);
+      const int64_t col_tiles = (N + kColLanes * VPT - 1) / (kColLanes * VPT);
+      TORCH_CHECK(col_tiles <= INT32_MAX, "relu_bwd_colsum_partial: N too large");
+      const dev_t* pdy = reinterpret_cast<const dev_t*>(dy.data_ptr<scalar_t>());
+      const dev_t* py = reinterpret_cast<const dev_t*>(yc.data_ptr<scalar_t>());
+      dev_t* pg = reinterpret_cast<dev_t*>(g.data_ptr<scalar_t>());
+      dim3 grid(static_cast<unsigned>(col_tiles), static_cast<unsigned>(G));
+      const bool vec = N % VPT == 0 && aligned16(pdy) && aligned16(py) && aligned16(pg);
+      if (vec) {
+        hipLaunchKernelGGL((relu_bwd_colsum_partial_kernel<dev_t, VPT, true>), grid,
+                           dim3(kBlockThreads), 0, stream, pdy, py, M, N,
+                           rows_per_group, pg, partial.data_ptr<float>());
+      } else {
+        hipLaunchKernelGGL((relu_bwd_colsum_partial_kernel<dev_t, VPT, false>), grid,
+                           dim3(kBlockThreads), 0, stream, pdy, py, M, N,
+                           rows_per_group, pg, partial.data_ptr<float>());
+      }
+    }
+  });
+  return partial;
+}
+
+static void check_relu_bwd_args(const at::Tensor& grad_out, const at::Tensor& y) {
+  TORCH_CHECK(grad_out.dim() == 2 && grad_out.is_cuda() && y.is_cuda());
+  TORCH_CHECK(grad_out.sizes() == y.sizes() && grad_out.scalar_type() == y.scalar_type());
+}
+
+std::tuple<at::Tensor, at::Tensor> relu_bwd_colsum_partial(const at::Tensor& grad_out,
+                                                           const at::Tensor& y) {
+  check_relu_bwd_args(grad_out, y);
+  int64_t M = grad_out.size(0), N = grad_out.size(1);
+  auto dy = grad_out.contiguous();
+  auto yc = y.contiguous();
+  auto g = at::empty_like(dy);
+  if (M == 0 || N == 0)
+    return {g, at::empty({0, N}, dy.options().dtype(at::kFloat))};
+  auto partial = launch_relu_bwd_partial(dy, yc, g);
+  return {g, partial};
 }
 
 std::tuple<at::Tensor, at::Tensor> relu_bwd_col_sum(const at::Tensor& grad_out,
                                                     const at::Tensor& y) {
-  TORCH_CHECK(grad_out.dim() == 2 && grad_out.is_cuda());
-  TORCH_CHECK(grad_out.sizes() == y.sizes() && grad_out.scalar_type() == y.scalar_type());
+  check_relu_bwd_args(grad_out, y);
   int64_t M = grad_out.size(0), N = grad_out.size(1);
   auto dy = grad_out.contiguous();
   auto yc = y.contiguous();
@@ -195,6 +289,7 @@ std::tuple<at::Tensor, at::Tensor> relu_bwd_col_sum(const at::Tensor& grad_out,
     db.zero_();
     return {g, db};
   }
+  auto partial = launch_relu_bwd_partial(dy, yc, g);
   auto stream = mlp_stream();
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kHalf, at::kBFloat16, dy.scalar_type(),
                                   "relu_bwd_col_sum", [&] {
@@ -202,67 +297,62 @@ std::tuple<at::Tensor, at::Tensor> relu_bwd_col_sum(const at::Tensor& grad_out,
       TORCH_CHECK(false, "fp64 unsupported");
     } else {
       using dev_t = typename DevType<scalar_t>::type;
-      constexpr int VPT = sizeof(dev_t) == 2 ? 8 : 4;
-      int64_t col_chunks = (N + VPT - 1) / VPT;
-      // enough (col-chunk, row-group) items to fill ~2048 blocks
-      int G = std::max<int>(1, std::min<int64_t>(
-          M, (static_cast<int64_t>(kMaxBlocks) * kBlockThreads) / std::max<int64_t>(col_chunks, 1)));
-      G = std::min(G, 1024);
-      int rows_per_group = (int)((M + G - 1) / G);
-      G = (int)((M + rows_per_group - 1) / rows_per_group);
-      auto partial = at::empty({(int64_t)G * N}, dy.options().dtype(at::kFloat));
-      int ftiles = (int)((N + kBlockThreads - 1) / kBlockThreads);
-      int grid = grid_for(col_chunks * G, kBlockThreads);
-      // same-box A/B: finish2 1.344 vs pair 1.326 ms/step — the one-kernel
-      // fold still loses to the two-kernel pair (the last-block tail runs
-      // on tiles4 blocks only); kept opt-in for future shapes
-      static const bool use_finish2 = [] {
-        const char* e = std::getenv("TREC_COLSUM_FINISH2");
-        return e && e[0] == '1';
-      }();
-      int tiles4 = (int)((N / 4 + kBlockThreads - 1) / kBlockThreads);
-      if (tiles4 < 1) tiles4 = 1;
-      at::Tensor counters;
-      int* cnt_ptr = nullptr;
-      if (G > 64 && use_finish2) {
-        // zeroed by block 0 of the partial kernel (same stream => ordered)
-        counters = at::empty({tiles4}, dy.options().dtype(at::kInt));
-        cnt_ptr = counters.data_ptr<int>();
-      }
-      hipLaunchKernelGGL((relu_bwd_colsum_partial_kernel<dev_t, VPT>), dim3(grid),
-                         dim3(kBlockThreads), 0, stream,
-                         reinterpret_cast<const dev_t*>(dy.data_ptr<scalar_t>()),
-                         reinterpret_cast<const dev_t*>(yc.data_ptr<scalar_t>()), M, N,
-                         rows_per_group, G,
-                         reinterpret_cast<dev_t*>(g.data_ptr<scalar_t>()),
-                         partial.data_ptr<float>(), cnt_ptr, tiles4);
-      if (G > 64 && use_finish2) {
-        constexpr int S = 32;
-        int seg_rows = (G + S - 1) / S;
-        auto seg = at::empty({(int64_t)S * N}, dy.options().dtype(at::kFloat));
-        hipLaunchKernelGGL((colsum_finish2_kernel<dev_t>), dim3(tiles4, S),
-                           dim3(kBlockThreads), 0, stream, partial.data_ptr<float>(),
-                           G, seg_rows, N, seg.data_ptr<float>(),
-                           cnt_ptr, S,
-                           reinterpret_cast<dev_t*>(db.data_ptr<scalar_t>()));
-      } else if (G > 64) {
-        constexpr int S = 32;
-        int seg_rows = (G + S - 1) / S;
-        auto seg = at::empty({(int64_t)S * N}, dy.options().dtype(at::kFloat));
-        hipLaunchKernelGGL(colsum_seg_f32_kernel, dim3(ftiles, S),
-                           dim3(kBlockThreads), 0, stream, partial.data_ptr<float>(),
-                           G, seg_rows, N, seg.data_ptr<float>());
-        hipLaunchKernelGGL((colsum_final_cast_kernel<dev_t>), dim3(ftiles),
-                           dim3(kBlockThreads), 0, stream, seg.data_ptr<float>(),
-                           S, N, reinterpret_cast<dev_t*>(db.data_ptr<scalar_t>()));
-      } else {
-        hipLaunchKernelGGL((colsum_final_cast_kernel<dev_t>), dim3(ftiles),
-                           dim3(kBlockThreads), 0, stream, partial.data_ptr<float>(),
-                           G, N, reinterpret_cast<dev_t*>(db.data_ptr<scalar_t>()));
-      }
+      int ftiles = (int)((N + kFoldCols - 1) / kFoldCols);
+      hipLaunchKernelGGL((colsum_final_cast_kernel<dev_t>), dim3(ftiles),
+                         dim3(kBlockThreads), 0, stream, partial.data_ptr<float>(),
+                         (int)partial.size(0), N,
+                         reinterpret_cast<dev_t*>(db.data_ptr<scalar_t>()));
     }
   });
   return {g, db};
+}
+
+// parts [S, N, K] (the split-K bmm output), partial [G, N] fp32 ->
+// dW [N, K] = sum_s parts[s], db [N] = sum_g partial[g], both in parts' dtype.
+std::tuple<at::Tensor, at::Tensor> splitk_fold_bias(const at::Tensor& parts,
+                                                    const at::Tensor& partial) {
+  TORCH_CHECK(parts.dim() == 3 && parts.is_cuda() && partial.is_cuda());
+  TORCH_CHECK(partial.dim() == 2 && partial.scalar_type() == at::kFloat);
+  TORCH_CHECK(partial.size(1) == parts.size(1),
+              "splitk_fold_bias: partial [G, N] must match parts [S, N, K]");
+  auto pc = parts.contiguous();
+  auto pp = partial.contiguous();
+  const int64_t S = pc.size(0), N = pc.size(1), K = pc.size(2);
+  const int64_t G = pp.size(0);
+  TORCH_CHECK(S <= INT32_MAX && G <= INT32_MAX);
+  auto dw = at::empty({N, K}, pc.options());
+  auto db = at::empty({N}, pc.options());
+  if (N == 0) return {dw, db};
+  const int64_t E = N * K;
+  auto stream = mlp_stream();
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::kHalf, at::kBFloat16, pc.scalar_type(),
+                                  "splitk_fold_bias", [&] {
+    if constexpr (std::is_same_v<scalar_t, double>) {
+      TORCH_CHECK(false, "fp64 unsupported");
+    } else {
+      using dev_t = typename DevType<scalar_t>::type;
+      constexpr int VPT = 16 / sizeof(dev_t);
+      const int64_t chunks = (E + VPT - 1) / VPT;
+      const int sum_blocks = E > 0 ? grid_for(chunks, kBlockThreads) : 0;
+      const int64_t fold_blocks = (N + kFoldCols - 1) / kFoldCols;
+      TORCH_CHECK(fold_blocks <= INT32_MAX - sum_blocks, "splitk_fold_bias: N too large");
+      const dev_t* pin = reinterpret_cast<const dev_t*>(pc.data_ptr<scalar_t>());
+      dev_t* pdw = reinterpret_cast<dev_t*>(dw.data_ptr<scalar_t>());
+      dev_t* pdb = reinterpret_cast<dev_t*>(db.data_ptr<scalar_t>());
+      dim3 grid(static_cast<unsigned>(sum_blocks + fold_blocks));
+      const bool vec = E % VPT == 0 && aligned16(pin) && aligned16(pdw);
+      if (vec) {
+        hipLaunchKernelGGL((splitk_fold_bias_kernel<dev_t, VPT, true>), grid,
+                           dim3(kBlockThreads), 0, stream, pin, (int)S, E, pdw,
+                           sum_blocks, pp.data_ptr<float>(), (int)G, N, pdb);
+      } else {
+        hipLaunchKernelGGL((splitk_fold_bias_kernel<dev_t, VPT, false>), grid,
+                           dim3(kBlockThreads), 0, stream, pin, (int)S, E, pdw,
+                           sum_blocks, pp.data_ptr<float>(), (int)G, N, pdb);
+      }
+    }
+  });
+  return {dw, db};
 }
 
 // relu mask only: g = dy * (y > 0) — one vectorized pass; the bias grad
