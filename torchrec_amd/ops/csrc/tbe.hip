@@ -1084,54 +1084,163 @@ std::tuple<at::Tensor, at::Tensor> tbe_backward_chunk_prep(const at::Tensor& seg
   return {chunk_offsets, total};
 }
 
-__device__ __forceinline__ int upper_bound_segment_i32(const int32_t* offs, int n, int32_t x) {
-  int lo = 0, hi = n;
-  while (hi - lo > 1) {
-    int mid = (lo + hi) >> 1;
-    if (offs[mid] <= x) lo = mid; else hi = mid;
+// third descriptor word of a run: where its first occurrence's grad row is
+// (a run of one occurrence goes from descriptor straight to the row) and D
+struct alignas(16) RunHead {
+  int64_t first_off;
+  int32_t D;
+  float first_scale;
+};
+
+// rows a slot keeps in flight between waits. 4 keeps the bench's fused
+// instance at 64 VGPRs (occupancy 8); 8 cost it 84 VGPRs, occupancy 5 and
+// 10 us per step (docs/KERNELS.md, Round 4). Loads outstanding per lane stay
+// at TREC_BWD_FLIGHT whatever CHUNKS is.
+#ifndef TREC_BWD_FLIGHT
+#define TREC_BWD_FLIGHT 4
+#endif
+template <int CHUNKS>
+constexpr int bwd_flight() {
+  return TREC_BWD_FLIGHT / CHUNKS > 0 ? TREC_BWD_FLIGHT / CHUNKS : 1;
+}
+
+// N occurrences j..j+N-1 of the current offset round: N row loads issued
+// back to back, then acc = fma(s, g, acc) in occurrence order. Straight-line
+// code: a lane outside the row (col4 * 4 >= D) loads the row's last vector
+// and skips the accumulate, so that no load sits behind a branch.
+template <typename g_t, int LPS, int CHUNKS, int N>
+__device__ __forceinline__ void gather_flight(
+    const g_t* __restrict__ grad, int64_t my_off, float my_s, bool scaled, int j, int D,
+    int sl, float4 (&acc)[CHUNKS]) {
+  float4 g[N][CHUNKS];
+  float s[N];
+  const int last4 = D / 4 - 1;
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const g_t* grow = grad + __shfl(my_off, j + u, LPS);
+    s[u] = scaled ? __shfl(my_s, j + u, LPS) : 1.f;
+#pragma unroll
+    for (int cc = 0; cc < CHUNKS; ++cc)
+      g[u][cc] = Vec4<g_t>::load(grow, min(cc * LPS + sl, last4));
   }
-  return lo;
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+#pragma unroll
+    for (int cc = 0; cc < CHUNKS; ++cc) {
+      int col4 = cc * LPS + sl;
+      if (col4 * 4 < D) {
+        acc[cc].x += s[u] * g[u][cc].x;
+        acc[cc].y += s[u] * g[u][cc].y;
+        acc[cc].z += s[u] * g[u][cc].z;
+        acc[cc].w += s[u] * g[u][cc].w;
+      }
+    }
+  }
+}
+
+// acc = fma(s_k, g_k, acc) over sorted positions k0..k1-1 in k order. The
+// slot's lanes fetch LPS grow_off (+ scale) entries in one coalesced load and
+// hand them round with __shfl; U rows are in flight at a time, and what is
+// left of a round goes in flights of 4, 2 and 1. Only the loads move: the
+// adds keep their order.
+template <typename g_t, int LPS, int CHUNKS>
+__device__ __forceinline__ void gather_run_rows(
+    const g_t* __restrict__ grad, const int64_t* __restrict__ grow_off,
+    const float* __restrict__ sorted_scale, int32_t k0, int32_t k1, int D, int sl,
+    float4 (&acc)[CHUNKS]) {
+  constexpr int U = bwd_flight<CHUNKS>();
+  static_assert(U <= 8 && LPS % U == 0, "a flight never straddles an offset round");
+  const bool scaled = sorted_scale != nullptr;
+  for (int32_t kb = k0; kb < k1; kb += LPS) {
+    const int cnt = min(LPS, k1 - kb);
+    int64_t my_off = 0;
+    float my_s = 1.f;
+    if (sl < cnt) {
+      my_off = grow_off[kb + sl];
+      if (scaled) my_s = sorted_scale[kb + sl];
+    }
+    int j = 0;
+    for (; j + U <= cnt; j += U)
+      gather_flight<g_t, LPS, CHUNKS, U>(grad, my_off, my_s, scaled, j, D, sl, acc);
+    if (U > 4 && cnt - j >= 4) {
+      gather_flight<g_t, LPS, CHUNKS, 4>(grad, my_off, my_s, scaled, j, D, sl, acc);
+      j += 4;
+    }
+    if (U > 2 && cnt - j >= 2) {
+      gather_flight<g_t, LPS, CHUNKS, 2>(grad, my_off, my_s, scaled, j, D, sl, acc);
+      j += 2;
+    }
+    if (U > 1 && cnt - j >= 1)
+      gather_flight<g_t, LPS, CHUNKS, 1>(grad, my_off, my_s, scaled, j, D, sl, acc);
+  }
+}
+
+// acc += scratch row c, for c = c0..c1-1 in ascending order, with the same
+// flights as the gather
+template <int LPS, int CHUNKS, int N>
+__device__ __forceinline__ void fold_flight(const float* __restrict__ scratch, int64_t max_D,
+                                            int32_t c, int D, int sl,
+                                            float4 (&acc)[CHUNKS]) {
+  float4 g[N][CHUNKS];
+  const int last4 = D / 4 - 1;
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const float4* srow = reinterpret_cast<const float4*>(scratch + (c + u) * max_D);
+#pragma unroll
+    for (int cc = 0; cc < CHUNKS; ++cc) g[u][cc] = srow[min(cc * LPS + sl, last4)];
+  }
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+#pragma unroll
+    for (int cc = 0; cc < CHUNKS; ++cc) {
+      int col4 = cc * LPS + sl;
+      if (col4 * 4 < D) {
+        acc[cc].x += g[u][cc].x;
+        acc[cc].y += g[u][cc].y;
+        acc[cc].z += g[u][cc].z;
+        acc[cc].w += g[u][cc].w;
+      }
+    }
+  }
+}
+
+template <int LPS, int CHUNKS>
+__device__ __forceinline__ void fold_chunk_partials(const float* __restrict__ scratch,
+                                                    int64_t max_D, int32_t c0, int32_t c1,
+                                                    int D, int sl, float4 (&acc)[CHUNKS]) {
+  constexpr int U = bwd_flight<CHUNKS>();
+  int32_t c = c0;
+  for (; c + U <= c1; c += U) fold_flight<LPS, CHUNKS, U>(scratch, max_D, c, D, sl, acc);
+  if (U > 4 && c1 - c >= 4) {
+    fold_flight<LPS, CHUNKS, 4>(scratch, max_D, c, D, sl, acc);
+    c += 4;
+  }
+  if (U > 2 && c1 - c >= 2) {
+    fold_flight<LPS, CHUNKS, 2>(scratch, max_D, c, D, sl, acc);
+    c += 2;
+  }
+  if (U > 1 && c1 - c >= 1) fold_flight<LPS, CHUNKS, 1>(scratch, max_D, c, D, sl, acc);
 }
 
 template <typename g_t, int LPS, int CHUNKS>
 __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_long_partial_kernel(
     const g_t* __restrict__ grad,
-    const int4* __restrict__ desc_a,   // per run: {k0, k1, c0, c1}
-    const int* __restrict__ desc_d,    // per run: D
-    const int64_t* __restrict__ grow_off,   // per sorted position: grad row offset
+    const int4* __restrict__ chunk_desc,     // per chunk: {k0, k1, D, run}
+    const int64_t* __restrict__ grow_off,    // per sorted position: grad row offset
     const float* __restrict__ sorted_scale,  // nullable, sorted order
-    const int32_t* __restrict__ num_runs_ptr,
-    const int32_t* __restrict__ chunk_offsets, const int32_t* __restrict__ total_chunks_ptr,
-    int chunk_size, int64_t max_D, float* __restrict__ scratch) {
+    const int32_t* __restrict__ total_chunks_ptr, int64_t max_D,
+    float* __restrict__ scratch) {
   int sl = threadIdx.x % LPS;
   int64_t slot = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / LPS;
   int64_t n_slots = (static_cast<int64_t>(gridDim.x) * blockDim.x) / LPS;
   int32_t total_chunks = *total_chunks_ptr;
-  int32_t num_runs = *num_runs_ptr;
   for (int64_t c = slot; c < total_chunks; c += n_slots) {
-    int r = upper_bound_segment_i32(chunk_offsets, num_runs, (int32_t)c);
-    int4 da = desc_a[r];
-    int32_t k0 = da.x + (c - da.z) * chunk_size;
-    int32_t k1 = min(da.y, k0 + chunk_size);
-    int D = desc_d[r];
+    int4 cd = chunk_desc[c];
+    int D = cd.z;
     float4 acc[CHUNKS];
 #pragma unroll
     for (int cc = 0; cc < CHUNKS; ++cc) acc[cc] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int32_t k = k0; k < k1; ++k) {
-      const g_t* grow = grad + grow_off[k];
-      float s = sorted_scale ? sorted_scale[k] : 1.f;
-#pragma unroll
-      for (int cc = 0; cc < CHUNKS; ++cc) {
-        int col4 = cc * LPS + sl;
-        if (col4 * 4 < D) {
-          float4 g = Vec4<g_t>::load(grow, col4);
-          acc[cc].x += s * g.x;
-          acc[cc].y += s * g.y;
-          acc[cc].z += s * g.z;
-          acc[cc].w += s * g.w;
-        }
-      }
-    }
+    gather_run_rows<g_t, LPS, CHUNKS>(grad, grow_off, sorted_scale, cd.x, cd.y, D, sl, acc);
     float4* srow = reinterpret_cast<float4*>(scratch + c * max_D);
 #pragma unroll
     for (int cc = 0; cc < CHUNKS; ++cc) {
@@ -1141,14 +1250,16 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_long_partial_kernel(
   }
 }
 
-// one streaming pass builds (a) a 36-byte descriptor per duplicate-index run
+// one streaming pass builds (a) a 48-byte descriptor per duplicate-index run
 // — collapsing the fused kernel's 7-deep dependent scalar chain
 // (seg_offsets -> sorted_linear -> table binary search -> chunk_offsets) to
 // three independent vector loads — and (b) the grad-row offset (+ scale) per
 // SORTED position, so the gather chain perm -> (row, col) -> grad row
-// becomes one sequential read + one row load. Measured motivation: with
-// ids made fully sequential the fused kernel only sped up 8% => it is
-// latency-chain bound, not DRAM-randomness bound.
+// becomes one sequential read + one row load, and (c) a descriptor
+// {k0, k1, D, run} per chunk of a long run, so the long-partial kernel looks
+// nothing up. Measured motivation: with ids made fully sequential the fused
+// kernel only sped up 8% => it is latency-chain bound, not
+// DRAM-randomness bound.
 __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_build_desc_kernel(
     const int32_t* __restrict__ seg_offsets, const int32_t* __restrict__ chunk_offsets,
     const int32_t* __restrict__ num_runs_ptr, const int64_t* __restrict__ sorted_linear,
@@ -1156,26 +1267,66 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_build_desc_kernel(
     const int64_t* __restrict__ pos_col, const float* __restrict__ pos_scale,
     int64_t grad_stride, const int64_t* __restrict__ table_row_offsets,
     const int64_t* __restrict__ table_elem_offsets, const int32_t* __restrict__ dims,
-    int T, int64_t n, int4* __restrict__ desc_a, longlong2* __restrict__ desc_b,
-    int* __restrict__ desc_d, int64_t* __restrict__ grow_off,
+    int T, int64_t n, int chunk_size, int4* __restrict__ desc_a,
+    longlong2* __restrict__ desc_b, RunHead* __restrict__ desc_c,
+    int4* __restrict__ chunk_desc, int64_t* __restrict__ grow_off,
     float* __restrict__ sorted_scale) {
+  // a run of more chunks than this has its chunk descriptors written by the
+  // whole wave, not by its own thread (the 3-row table: 683 chunks at B=65536)
+  constexpr int kOwnChunks = 16;
   int32_t num_runs = *num_runs_ptr;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n;
-       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    int32_t p = sort_perm[i];
-    grow_off[i] = static_cast<int64_t>(pos_row[p]) * grad_stride + pos_col[p];
-    if (sorted_scale) sorted_scale[i] = pos_scale[p];
+  const int lane = threadIdx.x & (kWaveSize - 1);
+  // the loop is wave-uniform (base is lane 0's index) so that the ballot
+  // below sees every lane of the wave
+  for (int64_t base = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x - lane;
+       base < n; base += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t i = base + lane;
+    if (i < n) {
+      int32_t p = sort_perm[i];
+      grow_off[i] = static_cast<int64_t>(pos_row[p]) * grad_stride + pos_col[p];
+      if (sorted_scale) sorted_scale[i] = pos_scale[p];
+    }
+    int32_t k0 = 0, k1 = 0, c0 = 0, nch = 0;
+    int D = 0;
     if (i < num_runs) {
-      int32_t k0 = seg_offsets[i], k1 = seg_offsets[i + 1];
+      k0 = seg_offsets[i];
+      k1 = seg_offsets[i + 1];
       int64_t lin = sorted_linear[k0];
+      int32_t p0 = sort_perm[k0];
       int t = upper_bound_segment(table_row_offsets, T, lin);
-      int D = dims[t];
-      desc_a[i] = make_int4(k0, k1, chunk_offsets[i], chunk_offsets[i + 1]);
+      D = dims[t];
+      c0 = chunk_offsets[i];
+      int32_t c1 = chunk_offsets[i + 1];
+      nch = c1 - c0;
+      desc_a[i] = make_int4(k0, k1, c0, c1);
       longlong2 b;
       b.x = lin;
       b.y = table_elem_offsets[t] + (lin - table_row_offsets[t]) * static_cast<int64_t>(D);
       desc_b[i] = b;
-      desc_d[i] = D;
+      RunHead h;
+      h.first_off = static_cast<int64_t>(pos_row[p0]) * grad_stride + pos_col[p0];
+      h.D = D;
+      h.first_scale = pos_scale ? pos_scale[p0] : 1.f;
+      desc_c[i] = h;
+      if (nch <= kOwnChunks) {
+        for (int j = 0; j < nch; ++j) {
+          int32_t ck = k0 + j * chunk_size;
+          chunk_desc[c0 + j] = make_int4(ck, min(k1, ck + chunk_size), D, (int)i);
+        }
+      }
+    }
+    uint64_t wide = __ballot(nch > kOwnChunks);
+    while (wide) {
+      const int src = __ffsll(static_cast<unsigned long long>(wide)) - 1;
+      wide &= wide - 1;
+      const int32_t sk0 = __shfl(k0, src, kWaveSize), sk1 = __shfl(k1, src, kWaveSize);
+      const int32_t sc0 = __shfl(c0, src, kWaveSize), sn = __shfl(nch, src, kWaveSize);
+      const int sD = __shfl(D, src, kWaveSize);
+      for (int j = lane; j < sn; j += kWaveSize) {
+        int32_t ck = sk0 + j * chunk_size;
+        chunk_desc[sc0 + j] =
+            make_int4(ck, min(sk1, ck + chunk_size), sD, (int)(base + src));
+      }
     }
   }
 }
@@ -1187,13 +1338,18 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_build_desc_kernel(
 // mode: 0 = SGD, 1 = rowwise Adagrad, 2 = dense grad (write grad_weights).
 // ---------------------------------------------------------------------------
 
-template <typename emb_t, typename g_t, int LPS, int CHUNKS>
+// ADAM = false serves modes 0, 1 and 2, ADAM = true modes 3 and 4: the
+// rowwise-Adagrad launch does not carry the Adam code or its prefetch
+// registers. Everything a run's update reads besides the gradient (momentum,
+// the weight or cache row, m1/m2) has its address in the descriptor, so those
+// loads are issued before the gather and are in flight with it.
+template <typename emb_t, typename g_t, int LPS, int CHUNKS, bool ADAM>
 __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_fused_kernel(
     emb_t* __restrict__ weights, float* __restrict__ momentum,
     const g_t* __restrict__ grad,
     const int4* __restrict__ desc_a,        // per run: {k0, k1, c0, c1}
     const longlong2* __restrict__ desc_b,   // per run: {lin, elem_base}
-    const int* __restrict__ desc_d,         // per run: D
+    const RunHead* __restrict__ desc_c,     // per run: {first grad row, D, first scale}
     const int64_t* __restrict__ grow_off,   // per sorted position
     const float* __restrict__ sorted_scale, // nullable, sorted order
     const int32_t* __restrict__ sort_perm,  // cache-locator path only
@@ -1209,54 +1365,66 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_fused_kernel(
   int64_t n_slots = (static_cast<int64_t>(gridDim.x) * blockDim.x) / LPS;
   int32_t num_runs = *num_runs_ptr;
   const uint64_t rng_base = rng_state ? (uint64_t)*rng_state : 0;
+  constexpr bool kPrefetchRows = CHUNKS <= 2;
   for (int64_t r = slot; r < num_runs; r += n_slots) {
     int4 da = desc_a[r];
     longlong2 dbv = desc_b[r];
+    RunHead head = desc_c[r];
     int32_t k0 = da.x, k1 = da.y;
     int64_t lin = dbv.x;
-    int D = desc_d[r];
-    float4 acc[CHUNKS];
-#pragma unroll
-    for (int c = 0; c < CHUNKS; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (da.w > da.z) {
-      // long run: sum phase-1 chunk partials in order (deterministic)
-      for (int32_t c = da.z; c < da.w; ++c) {
-        const float4* srow = reinterpret_cast<const float4*>(scratch + c * max_D);
-#pragma unroll
-        for (int cc = 0; cc < CHUNKS; ++cc) {
-          int col4 = cc * LPS + sl;
-          if (col4 * 4 < D) {
-            float4 g = srow[col4];
-            acc[cc].x += g.x;
-            acc[cc].y += g.y;
-            acc[cc].z += g.z;
-            acc[cc].w += g.w;
-          }
-        }
-      }
-    } else {
-      for (int32_t k = k0; k < k1; ++k) {
-        const g_t* grow = grad + grow_off[k];
-        float s = sorted_scale ? sorted_scale[k] : 1.f;
-#pragma unroll
-        for (int c = 0; c < CHUNKS; ++c) {
-          int col4 = c * LPS + sl;
-          if (col4 * 4 < D) {
-            float4 g = Vec4<g_t>::load(grow, col4);
-            acc[c].x += s * g.x;
-            acc[c].y += s * g.y;
-            acc[c].z += s * g.z;
-            acc[c].w += s * g.w;
-          }
-        }
-      }
-    }
+    int D = head.D;
     // weight row: emb_t in the table, fp32 if the row sits in the lxu cache
     emb_t* wrow = weights + dbv.y;
     float* crow = nullptr;
     int32_t cloc = cache_loc ? cache_loc[sort_perm[k0]] : -1;
     if (cloc >= 0) crow = cache_weights + static_cast<int64_t>(cloc) * cache_stride;
-    if (mode == 1) {
+    // early loads of what the update reads (wide rows would hold too many
+    // registers across the gather: they load at the update as before)
+    float row_state = 0.f;  // momentum[lin] (mode 1) or m2[lin] (mode 4)
+    float4 w_pre[kPrefetchRows ? CHUNKS : 1];
+    float4 m1_pre[kPrefetchRows && ADAM ? CHUNKS : 1];
+    float4 m2_pre[kPrefetchRows && ADAM ? CHUNKS : 1];
+    if (!ADAM && mode == 1) row_state = momentum[lin];
+    if (ADAM && mode == 4) row_state = m2[lin];
+    if (kPrefetchRows && (ADAM || mode != 2)) {
+#pragma unroll
+      for (int c = 0; c < CHUNKS; ++c) {
+        int col4 = c * LPS + sl;
+        if (col4 * 4 < D) {
+          w_pre[c] = crow ? Vec4<float>::load(crow, col4) : Vec4<emb_t>::load(wrow, col4);
+          if (ADAM) {
+            m1_pre[c] = reinterpret_cast<const float4*>(m1 + dbv.y)[col4];
+            if (mode == 3) m2_pre[c] = reinterpret_cast<const float4*>(m2 + dbv.y)[col4];
+          }
+        }
+      }
+    }
+    float4 acc[CHUNKS];
+#pragma unroll
+    for (int c = 0; c < CHUNKS; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (da.w > da.z) {
+      // long run: sum phase-1 chunk partials in ascending chunk order
+      // (deterministic)
+      fold_chunk_partials<LPS, CHUNKS>(scratch, max_D, da.z, da.w, D, sl, acc);
+    } else if (k1 - k0 == 1) {
+      // one occurrence (most runs): descriptor -> grad row, no grow_off hop
+      const g_t* grow = grad + head.first_off;
+      float s = head.first_scale;
+#pragma unroll
+      for (int c = 0; c < CHUNKS; ++c) {
+        int col4 = c * LPS + sl;
+        if (col4 * 4 < D) {
+          float4 g = Vec4<g_t>::load(grow, col4);
+          acc[c].x += s * g.x;
+          acc[c].y += s * g.y;
+          acc[c].z += s * g.z;
+          acc[c].w += s * g.w;
+        }
+      }
+    } else {
+      gather_run_rows<g_t, LPS, CHUNKS>(grad, grow_off, sorted_scale, k0, k1, D, sl, acc);
+    }
+    if (!ADAM && mode == 1) {
       // rowwise Adagrad: m += mean(g^2); w -= lr * g / (sqrt(m) + eps)
       float gsq = 0.f;
 #pragma unroll
@@ -1267,14 +1435,16 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_fused_kernel(
                  acc[c].w * acc[c].w;
       }
       gsq = group_reduce_sum<LPS>(gsq);
-      float m = momentum[lin] + gsq / static_cast<float>(D);
+      float m = row_state + gsq / static_cast<float>(D);
       if (sl == 0) momentum[lin] = m;
       float step = lr / (sqrtf(m) + eps);
 #pragma unroll
       for (int c = 0; c < CHUNKS; ++c) {
         int col4 = c * LPS + sl;
         if (col4 * 4 < D) {
-          float4 w = crow ? Vec4<float>::load(crow, col4) : Vec4<emb_t>::load(wrow, col4);
+          float4 w = kPrefetchRows ? w_pre[kPrefetchRows ? c : 0]
+                                   : crow ? Vec4<float>::load(crow, col4)
+                                          : Vec4<emb_t>::load(wrow, col4);
           w.x -= step * acc[c].x;
           w.y -= step * acc[c].y;
           w.z -= step * acc[c].z;
@@ -1284,12 +1454,14 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_fused_kernel(
                                   stochastic != 0);
         }
       }
-    } else if (mode == 0) {
+    } else if (!ADAM && mode == 0) {
 #pragma unroll
       for (int c = 0; c < CHUNKS; ++c) {
         int col4 = c * LPS + sl;
         if (col4 * 4 < D) {
-          float4 w = crow ? Vec4<float>::load(crow, col4) : Vec4<emb_t>::load(wrow, col4);
+          float4 w = kPrefetchRows ? w_pre[kPrefetchRows ? c : 0]
+                                   : crow ? Vec4<float>::load(crow, col4)
+                                          : Vec4<emb_t>::load(wrow, col4);
           w.x -= lr * acc[c].x;
           w.y -= lr * acc[c].y;
           w.z -= lr * acc[c].z;
@@ -1299,7 +1471,12 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_fused_kernel(
                                   stochastic != 0);
         }
       }
-    } else if (mode == 3 || mode == 4) {
+    } else if (ADAM) {
+      // Which product of a * b + c * d folds into the fma was the compiler's
+      // pick and moved with the surrounding code. It is written out here, as
+      // the kernel computed it before the mode split, so that the states stay
+      // bit for bit what they were.
+#pragma clang fp contract(off)
       // Adam (mode 3: elementwise m2) / partial-rowwise Adam (mode 4: one m2
       // scalar per row = beta2-EMA of mean(g^2)). Reference semantics: TBE
       // fused optimizers (batched_embedding_kernel.py:36-53 imports).
@@ -1318,7 +1495,7 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_fused_kernel(
                    acc[c].w * acc[c].w;
         }
         gsq = group_reduce_sum<LPS>(gsq);
-        float v = beta2 * m2[lin] + (1.f - beta2) * gsq / static_cast<float>(D);
+        float v = fmaf(beta2, row_state, (1.f - beta2) * gsq / static_cast<float>(D));
         if (sl == 0) m2[lin] = v;
         inv_sqrt_row = 1.f / (sqrtf(v * bc2) + eps);
       }
@@ -1327,20 +1504,20 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_fused_kernel(
         int col4 = c * LPS + sl;
         if (col4 * 4 < D) {
           float4* m1p = reinterpret_cast<float4*>(m1 + ebase);
-          float4 mv = m1p[col4];
-          mv.x = beta1 * mv.x + (1.f - beta1) * acc[c].x;
-          mv.y = beta1 * mv.y + (1.f - beta1) * acc[c].y;
-          mv.z = beta1 * mv.z + (1.f - beta1) * acc[c].z;
-          mv.w = beta1 * mv.w + (1.f - beta1) * acc[c].w;
+          float4 mv = kPrefetchRows ? m1_pre[kPrefetchRows ? c : 0] : m1p[col4];
+          mv.x = fmaf(1.f - beta1, acc[c].x, beta1 * mv.x);
+          mv.y = fmaf(1.f - beta1, acc[c].y, beta1 * mv.y);
+          mv.z = fmaf(1.f - beta1, acc[c].z, beta1 * mv.z);
+          mv.w = fmaf(1.f - beta1, acc[c].w, beta1 * mv.w);
           m1p[col4] = mv;
           float4 upd;
           if (mode == 3) {
             float4* m2p = reinterpret_cast<float4*>(m2 + ebase);
-            float4 vv = m2p[col4];
-            vv.x = beta2 * vv.x + (1.f - beta2) * acc[c].x * acc[c].x;
-            vv.y = beta2 * vv.y + (1.f - beta2) * acc[c].y * acc[c].y;
-            vv.z = beta2 * vv.z + (1.f - beta2) * acc[c].z * acc[c].z;
-            vv.w = beta2 * vv.w + (1.f - beta2) * acc[c].w * acc[c].w;
+            float4 vv = kPrefetchRows ? m2_pre[kPrefetchRows ? c : 0] : m2p[col4];
+            vv.x = fmaf((1.f - beta2) * acc[c].x, acc[c].x, beta2 * vv.x);
+            vv.y = fmaf((1.f - beta2) * acc[c].y, acc[c].y, beta2 * vv.y);
+            vv.z = fmaf((1.f - beta2) * acc[c].z, acc[c].z, beta2 * vv.z);
+            vv.w = fmaf((1.f - beta2) * acc[c].w, acc[c].w, beta2 * vv.w);
             m2p[col4] = vv;
             upd.x = lr * mv.x * bc1 / (sqrtf(vv.x * bc2) + eps);
             upd.y = lr * mv.y * bc1 / (sqrtf(vv.y * bc2) + eps);
@@ -1352,7 +1529,9 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_fused_kernel(
             upd.z = lr * mv.z * bc1 * inv_sqrt_row;
             upd.w = lr * mv.w * bc1 * inv_sqrt_row;
           }
-          float4 w = crow ? Vec4<float>::load(crow, col4) : Vec4<emb_t>::load(wrow, col4);
+          float4 w = kPrefetchRows ? w_pre[kPrefetchRows ? c : 0]
+                                   : crow ? Vec4<float>::load(crow, col4)
+                                          : Vec4<emb_t>::load(wrow, col4);
           w.x -= upd.x;
           w.y -= upd.y;
           w.z -= upd.z;
@@ -1362,7 +1541,7 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_fused_kernel(
                                   stochastic != 0);
         }
       }
-    } else {
+    } else if (!ADAM) {
       emb_t* gw = grad_weights + dbv.y;
 #pragma unroll
       for (int c = 0; c < CHUNKS; ++c) {
@@ -1396,7 +1575,9 @@ static void launch_tbe_bwd(
   auto opts_i = sorted_linear.options().dtype(at::kInt);
   auto desc_a_t = at::empty({n * 4}, opts_i);
   auto desc_b_t = at::empty({n * 2}, sorted_linear.options());
-  auto desc_d_t = at::empty({n}, opts_i);
+  auto desc_c_t = at::empty({n * 2}, sorted_linear.options());
+  // scratch holds max_chunks rows of max_D: one chunk descriptor per row
+  auto chunk_desc_t = at::empty({scratch.numel() / max_D * 4}, opts_i);
   auto grow_off_t = at::empty({n}, sorted_linear.options());
   at::Tensor sorted_scale_t;
   float* sscale_ptr = nullptr;
@@ -1406,6 +1587,8 @@ static void launch_tbe_bwd(
   }
   int4* desc_a_p = reinterpret_cast<int4*>(desc_a_t.data_ptr<int32_t>());
   longlong2* desc_b_p = reinterpret_cast<longlong2*>(desc_b_t.data_ptr<int64_t>());
+  RunHead* desc_c_p = reinterpret_cast<RunHead*>(desc_c_t.data_ptr<int64_t>());
+  int4* chunk_desc_p = reinterpret_cast<int4*>(chunk_desc_t.data_ptr<int32_t>());
   hipLaunchKernelGGL(tbe_bwd_build_desc_kernel, dim3(grid_for(n, kBlockThreads)),
                      dim3(kBlockThreads), 0, stream,
                      seg_offsets.data_ptr<int32_t>(), chunk_offsets.data_ptr<int32_t>(),
@@ -1414,27 +1597,28 @@ static void launch_tbe_bwd(
                      pos_col.data_ptr<int64_t>(), scale_ptr, grad.size(1),
                      table_row_offsets.data_ptr<int64_t>(),
                      table_elem_offsets.data_ptr<int64_t>(), dims.data_ptr<int32_t>(), T,
-                     n, desc_a_p, desc_b_p, desc_d_t.data_ptr<int32_t>(),
+                     n, chunk_size, desc_a_p, desc_b_p, desc_c_p, chunk_desc_p,
                      grow_off_t.data_ptr<int64_t>(), sscale_ptr);
+#define TBE_BWD_FUSED(LPS, CHUNKS, ADAM)                                                      \
+  hipLaunchKernelGGL((tbe_bwd_fused_kernel<emb_t, g_t, LPS, CHUNKS, ADAM>), dim3(grid),      \
+                     dim3(kBlockThreads),                                                    \
+                     0, stream, reinterpret_cast<emb_t*>(uvm_ptr<host_w_t>(weights)),        \
+                     uvm_ptr<float>(momentum),                                               \
+                     grad_ptr, desc_a_p, desc_b_p, desc_c_p,                                 \
+                     grow_off_t.data_ptr<int64_t>(), sscale_ptr,                             \
+                     sort_perm.data_ptr<int32_t>(),                                          \
+                     num_runs.data_ptr<int32_t>(), scratch.data_ptr<float>(), max_D,         \
+                     lr, eps, mode, gw_ptr, cache_w_ptr,                                     \
+                     cache_loc_ptr, max_D, m1_ptr, m2_ptr, beta1, beta2, iter_ptr,           \
+                     rng_ptr, stochastic)
 #define TBE_BWD_LAUNCH(LPS, CHUNKS)                                                          \
   do {                                                                                       \
     hipLaunchKernelGGL((tbe_bwd_long_partial_kernel<g_t, LPS, CHUNKS>), dim3(grid_long),     \
-                       dim3(kBlockThreads), 0, stream, grad_ptr, desc_a_p,                   \
-                       desc_d_t.data_ptr<int32_t>(), grow_off_t.data_ptr<int64_t>(),         \
-                       sscale_ptr, num_runs.data_ptr<int32_t>(),                             \
-                       chunk_offsets.data_ptr<int32_t>(), total_chunks.data_ptr<int32_t>(),  \
-                       chunk_size, max_D, scratch.data_ptr<float>());                        \
-    hipLaunchKernelGGL((tbe_bwd_fused_kernel<emb_t, g_t, LPS, CHUNKS>), dim3(grid),          \
-                       dim3(kBlockThreads),                                                  \
-                       0, stream, reinterpret_cast<emb_t*>(uvm_ptr<host_w_t>(weights)),      \
-                       uvm_ptr<float>(momentum),                                             \
-                       grad_ptr, desc_a_p, desc_b_p, desc_d_t.data_ptr<int32_t>(),           \
+                       dim3(kBlockThreads), 0, stream, grad_ptr, chunk_desc_p,               \
                        grow_off_t.data_ptr<int64_t>(), sscale_ptr,                           \
-                       sort_perm.data_ptr<int32_t>(),                                        \
-                       num_runs.data_ptr<int32_t>(), scratch.data_ptr<float>(), max_D,       \
-                       lr, eps, mode, gw_ptr, cache_w_ptr,                                   \
-                       cache_loc_ptr, max_D, m1_ptr, m2_ptr, beta1, beta2, iter_ptr,         \
-                       rng_ptr, stochastic);                                                 \
+                       total_chunks.data_ptr<int32_t>(), max_D, scratch.data_ptr<float>());  \
+    if (mode == 3 || mode == 4) TBE_BWD_FUSED(LPS, CHUNKS, true);                            \
+    else TBE_BWD_FUSED(LPS, CHUNKS, false);                                                  \
   } while (0)
   if (lps == 16) TBE_BWD_LAUNCH(16, 1);
   else if (lps == 32) TBE_BWD_LAUNCH(32, 1);
@@ -1445,6 +1629,7 @@ static void launch_tbe_bwd(
     default: TBE_BWD_LAUNCH(64, 8); break;
   }
 #undef TBE_BWD_LAUNCH
+#undef TBE_BWD_FUSED
 }
 
 template <typename emb_t, typename host_w_t>
