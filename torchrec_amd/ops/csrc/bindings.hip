@@ -68,6 +68,19 @@ void tbe_backward_fused(at::Tensor weights, at::Tensor momentum, const at::Tenso
                         at::Tensor m1, at::Tensor m2, double beta1, double beta2,
                         const at::Tensor& iter_t, const at::Tensor& rng_state,
                         bool stochastic);
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> tbe_backward_plan_sort(
+    const at::Tensor& offsets, const at::Tensor& indices, const at::Tensor& feat_d_out,
+    const at::Tensor& feat_row_offset, int64_t B, int64_t F, int64_t end_bit,
+    int64_t capacity);
+at::Tensor tbe_backward_planned(
+    at::Tensor weights, at::Tensor momentum, const at::Tensor& grad,
+    const at::Tensor& indices, const at::Tensor& offsets, const at::Tensor& feat_d_out,
+    const at::Tensor& feat_row_offset, int64_t B, int64_t F, int64_t end_bit,
+    int64_t capacity, const at::Tensor& pos_scale, const at::Tensor& table_row_offsets,
+    const at::Tensor& table_elem_offsets, const at::Tensor& dims, int64_t max_D, double lr,
+    double eps, int64_t mode, at::Tensor grad_weights, at::Tensor cache_weights,
+    const at::Tensor& cache_loc, at::Tensor m1, at::Tensor m2, double beta1, double beta2,
+    const at::Tensor& iter_t, const at::Tensor& rng_state, bool stochastic);
 at::Tensor gather_run_heads(const at::Tensor& sorted_linear, const at::Tensor& seg_offsets,
                             const at::Tensor& num_runs);
 at::Tensor tbe_grad_per_sample_weights(const at::Tensor& weights,
@@ -210,6 +223,18 @@ TORCH_LIBRARY(trec_amd, m) {
       " Tensor(c!) grad_weights, Tensor(d!) cache_weights, Tensor cache_loc,"
       " Tensor(e!) m1, Tensor(f!) m2, float beta1, float beta2, Tensor iter_t,"
       " Tensor rng_state, bool stochastic) -> ()");
+  m.def(
+      "tbe_backward_plan_sort(Tensor offsets, Tensor indices, Tensor feat_d_out,"
+      " Tensor feat_row_offset, int B, int F, int end_bit, int capacity)"
+      " -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def(
+      "tbe_backward_planned(Tensor(a!) weights, Tensor(b!) momentum, Tensor grad,"
+      " Tensor indices, Tensor offsets, Tensor feat_d_out, Tensor feat_row_offset, int B,"
+      " int F, int end_bit, int capacity, Tensor pos_scale, Tensor table_row_offsets,"
+      " Tensor table_elem_offsets, Tensor dims, int max_D, float lr, float eps, int mode,"
+      " Tensor(c!) grad_weights, Tensor(d!) cache_weights, Tensor cache_loc,"
+      " Tensor(e!) m1, Tensor(f!) m2, float beta1, float beta2, Tensor iter_t,"
+      " Tensor rng_state, bool stochastic) -> Tensor");
   m.def("gather_run_heads(Tensor sorted_linear, Tensor seg_offsets, Tensor num_runs) -> Tensor");
   m.def(
       "lxu_cache_populate(Tensor(a!) host_weights, Tensor table_row_offsets,"
@@ -289,6 +314,8 @@ TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
   m.impl("tbe_backward_prep", trec_amd::tbe_backward_prep);
   m.impl("tbe_bag_metadata", trec_amd::tbe_bag_metadata);
   m.impl("tbe_backward_fused", trec_amd::tbe_backward_fused);
+  m.impl("tbe_backward_plan_sort", trec_amd::tbe_backward_plan_sort);
+  m.impl("tbe_backward_planned", trec_amd::tbe_backward_planned);
   m.impl("tbe_grad_per_sample_weights", trec_amd::tbe_grad_per_sample_weights);
   m.impl("gather_run_heads", trec_amd::gather_run_heads);
   m.impl("lxu_cache_populate", trec_amd::lxu_cache_populate);

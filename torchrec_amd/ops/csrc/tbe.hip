@@ -848,6 +848,321 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> seg_sort_pairs_2level(
   return {sorted64, perm, overflow};
 }
 
+// ---------------------------------------------------------------------------
+// planned backward, sort half: the same two-level sort with the bag metadata
+// folded into the tile sort and 4-way rank merges instead of pairwise co-rank
+// rounds. A tile knows its segment f, so it forms the key
+// indices[i] + feat_row_offset[f] in registers (no int64 `linear` array) and
+// finds each position's bag among the B bags of f. The merge ranks every
+// element directly: x at local index i of run r lands at
+//   i + sum_{q<r} upper_bound(run_q, x) + sum_{q>r} lower_bound(run_q, x)
+// within its group of up to four runs (ties go to the lower run, which is the
+// stable order the pairwise rounds produce).
+// ---------------------------------------------------------------------------
+
+constexpr int kMergeItems = 4;
+constexpr int kMergeChunk = kTileThreads * kMergeItems;
+constexpr int kMergeLdsKeys = 8192;  // a group of four 2048-key tiles: 32 KB
+
+// DIRECT: the segment fits this one tile, so the final int64 keys and int32
+// perm are written here. clear_ws[0..clear_n) are the lookback workspaces of
+// the scan kernels that follow on the stream; they must be zero before those
+// kernels start, and a kernel boundary orders this clear before them.
+template <int ITEMS, bool DIRECT>
+__global__ void __launch_bounds__(kTileThreads) plan_tile_sort_kernel(
+    const int64_t* __restrict__ indices, const int64_t* __restrict__ offsets,
+    const int64_t* __restrict__ feat_d_out, const int64_t* __restrict__ feat_row_offset,
+    int B, int tiles_per_seg, int end_bit, int64_t capacity, int bag_len_hint,
+    uint32_t* __restrict__ keys_out, uint32_t* __restrict__ perm_out,
+    int64_t* __restrict__ keys_out64, int32_t* __restrict__ perm_out_final,
+    int32_t* __restrict__ pos_row, int64_t* __restrict__ pos_col,
+    int32_t* __restrict__ seg_overflow, uint64_t* __restrict__ clear_ws, int clear_n) {
+  constexpr int TS = kTileThreads * ITEMS;
+  using sorter = rocprim::block_radix_sort<uint32_t, kTileThreads, ITEMS, uint32_t>;
+  __shared__ typename sorter::storage_type storage;
+  for (int w = blockIdx.x * kTileThreads + threadIdx.x; w < clear_n;
+       w += gridDim.x * kTileThreads)
+    clear_ws[w] = 0;
+  int seg = blockIdx.x / tiles_per_seg;
+  int tile = blockIdx.x - seg * tiles_per_seg;
+  const int64_t bag0 = static_cast<int64_t>(seg) * B;
+  int64_t lo = offsets[bag0];
+  int64_t hi = offsets[bag0 + B];
+  if (tile == 0 && threadIdx.x == 0) seg_overflow[seg] = (hi - lo > capacity) ? 1 : 0;
+  int64_t t0 = lo + static_cast<int64_t>(tile) * TS;
+  if (t0 >= hi) return;
+  int count = static_cast<int>(min(hi - t0, (int64_t)TS));
+  const int64_t row_off = feat_row_offset[seg];
+  const int64_t d_out = feat_d_out[seg];
+  uint32_t keys[ITEMS];
+  uint32_t vals[ITEMS];
+  // the hinted bag is where position i lies when every bag before it is full;
+  // both of its bounds load at once, for all ITEMS positions
+  int row[ITEMS];
+  int64_t hlo[ITEMS], hhi[ITEMS];
+  const int64_t* seg_off = offsets + bag0;
+#pragma unroll
+  for (int i = 0; i < ITEMS; ++i) {
+    int k = static_cast<int>(threadIdx.x) * ITEMS + i;  // blocked
+    // loads go to a clamped, valid position so that none sits behind a branch
+    const int64_t pc = t0 + min(k, count - 1);
+    const int64_t idx = indices[pc];
+    row[i] = min(static_cast<int>(pc - lo) / bag_len_hint, B - 1);
+    hlo[i] = seg_off[row[i]];
+    hhi[i] = seg_off[row[i] + 1];
+    keys[i] = k < count ? static_cast<uint32_t>(idx + row_off) : 0xFFFFFFFFu;
+    vals[i] = k < count ? static_cast<uint32_t>(t0 + k) : 0xFFFFFFFFu;
+  }
+  bool miss = false;
+#pragma unroll
+  for (int i = 0; i < ITEMS; ++i) {
+    int k = static_cast<int>(threadIdx.x) * ITEMS + i;
+    if (k < count && !(hlo[i] <= t0 + k && t0 + k < hhi[i])) {
+      row[i] = -1;
+      miss = true;
+    }
+  }
+  if (miss) {
+    // the search proper: the number of bags of this segment that end at or
+    // before position p, built bit by bit so that all ITEMS searches step
+    // together and their loads are in flight at once
+    int top = 1;
+    while (top < B) top <<= 1;
+    int cnt[ITEMS];
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) cnt[i] = 0;
+    for (int s = top; s > 0; s >>= 1) {
+#pragma unroll
+      for (int i = 0; i < ITEMS; ++i) {
+        int k = static_cast<int>(threadIdx.x) * ITEMS + i;
+        const int end = cnt[i] + s;
+        const bool ended = seg_off[min(end, B)] <= t0 + k;
+        cnt[i] = (end <= B && ended) ? end : cnt[i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i)
+      if (row[i] < 0) row[i] = cnt[i];
+  }
+#pragma unroll
+  for (int i = 0; i < ITEMS; ++i) {
+    int k = static_cast<int>(threadIdx.x) * ITEMS + i;
+    if (k < count) {
+      pos_row[t0 + k] = row[i];
+      pos_col[t0 + k] = d_out;
+    }
+  }
+  sorter().sort(keys, vals, storage, 0u, static_cast<unsigned>(end_bit));
+#pragma unroll
+  for (int i = 0; i < ITEMS; ++i) {
+    int k = static_cast<int>(threadIdx.x) * ITEMS + i;
+    if (k < count) {
+      if (DIRECT) {
+        keys_out64[t0 + k] = static_cast<int64_t>(keys[i]);
+        perm_out_final[t0 + k] = static_cast<int32_t>(vals[i]);
+      } else {
+        keys_out[t0 + k] = keys[i];
+        perm_out[t0 + k] = vals[i];
+      }
+    }
+  }
+}
+
+// one merge round: groups of four consecutive sorted runs of run_len (a power
+// of two; the last group may have fewer runs, the last run may be short)
+// become one run each. LDS: 4 * run_len <= kMergeLdsKeys, the block stages
+// its whole group's keys and searches LDS; otherwise the searches probe the
+// L2-resident arrays. kMergeChunk divides run_len, so a block's elements all
+// come from one run r of one group. Each search builds its count bit by bit
+// (log2(run_len) + 1 steps whatever the data), so the three searches of all
+// kMergeItems elements step together with their loads in flight at once.
+template <bool LDS, bool OUT64>
+__global__ void __launch_bounds__(kTileThreads) seg_merge4_kernel(
+    const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
+    const int64_t* __restrict__ offsets, int B, int chunks_per_seg, int run_len,
+    uint32_t* __restrict__ keys_out32, int64_t* __restrict__ keys_out64,
+    uint32_t* __restrict__ vals_out32, int32_t* __restrict__ vals_out32_final) {
+  __shared__ uint32_t sK[LDS ? kMergeLdsKeys : 1];
+  int seg = blockIdx.x / chunks_per_seg;
+  int chunk = blockIdx.x - seg * chunks_per_seg;
+  int64_t lo = offsets[static_cast<int64_t>(seg) * B];
+  int64_t hi = offsets[static_cast<int64_t>(seg + 1) * B];
+  // a segment longer than the capacity is sorted up to the capacity only
+  int seg_len = static_cast<int>(min(hi - lo, (int64_t)chunks_per_seg * kMergeChunk));
+  int p0 = chunk * kMergeChunk;
+  if (p0 >= seg_len) return;
+  const int group_w = 4 * run_len;
+  const int gbase = (p0 / group_w) * group_w;
+  const int glen = min(group_w, seg_len - gbase);
+  const int r = (p0 - gbase) / run_len;
+  const uint32_t* gk = keys_in + lo + gbase;
+  const uint32_t* K = gk;
+  if constexpr (LDS) {
+    // eight loads in flight per thread (clamped index, guarded LDS store)
+    for (int i0 = threadIdx.x; i0 < glen; i0 += 8 * kTileThreads) {
+      uint32_t t[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) t[u] = gk[min(i0 + u * kTileThreads, glen - 1)];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (i0 + u * kTileThreads < glen) sK[i0 + u * kTileThreads] = t[u];
+    }
+    __syncthreads();
+    K = sK;
+  }
+  uint32_t x[kMergeItems];
+  uint32_t vv[kMergeItems];
+  int rank[kMergeItems];
+  int cnt[kMergeItems][4];
+#pragma unroll
+  for (int v = 0; v < kMergeItems; ++v) {
+    int p = p0 + v * kTileThreads + static_cast<int>(threadIdx.x);
+    bool ok = p < seg_len;
+    x[v] = ok ? K[p - gbase] : 0u;
+    vv[v] = ok ? vals_in[lo + p] : 0u;
+    rank[v] = p - gbase - r * run_len;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) cnt[v][q] = 0;
+  }
+  // no branch in the step: every probe goes to a clamped, valid index (an
+  // empty run, and the element's own run, probe the block's own run and
+  // count nothing), so the probes of one step are all in flight together
+  for (int s = run_len; s > 0; s >>= 1) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      // run q holds qlen keys; count those below x (at or below, for q < r)
+      const int qlen = (q == r) ? 0 : max(0, min(run_len, glen - q * run_len));
+      const uint32_t* run = K + (qlen > 0 ? q : r) * run_len;
+      const int qmax = max(qlen, 1);
+#pragma unroll
+      for (int v = 0; v < kMergeItems; ++v) {
+        const int end = cnt[v][q] + s;
+        const uint32_t kv = run[min(end, qmax) - 1];
+        const bool below = q < r ? (kv <= x[v]) : (kv < x[v]);
+        cnt[v][q] = (end <= qlen && below) ? end : cnt[v][q];
+      }
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < kMergeItems; ++v) {
+    int p = p0 + v * kTileThreads + static_cast<int>(threadIdx.x);
+    if (p < seg_len) {
+      int dst = rank[v];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) dst += cnt[v][q];
+      int64_t out_idx = lo + gbase + dst;
+      if (OUT64) {
+        keys_out64[out_idx] = static_cast<int64_t>(x[v]);
+        vals_out32_final[out_idx] = static_cast<int32_t>(vv[v]);
+      } else {
+        keys_out32[out_idx] = x[v];
+        vals_out32[out_idx] = vv[v];
+      }
+    }
+  }
+}
+
+namespace {
+struct PlanSorted {
+  at::Tensor sorted64, perm, pos_row, pos_col, seg_overflow;
+};
+
+// sort + metadata (+ merge rounds) of the planned backward. clear_ws (may be
+// null) is zeroed by the first kernel for the scans that follow.
+PlanSorted plan_sort_launch(const at::Tensor& offsets, const at::Tensor& indices,
+                            const at::Tensor& feat_d_out, const at::Tensor& feat_row_offset,
+                            int64_t B, int64_t F, int64_t end_bit, int64_t capacity,
+                            uint64_t* clear_ws, int clear_n, hipStream_t stream) {
+  TORCH_CHECK(indices.is_cuda() && indices.scalar_type() == at::kLong);
+  TORCH_CHECK(offsets.scalar_type() == at::kLong && offsets.numel() == F * B + 1);
+  TORCH_CHECK(end_bit <= 32, "segmented sort requires 32-bit ids");
+  TORCH_CHECK(B > 0 && capacity > 0 && capacity < (int64_t(1) << 30));
+  int64_t n = indices.numel();
+  auto opts32 = indices.options().dtype(at::kInt);
+  PlanSorted out;
+  out.sorted64 = at::empty({n}, indices.options());
+  out.perm = at::empty({n}, opts32);
+  out.pos_row = at::empty({n}, opts32);
+  out.pos_col = at::empty({n}, indices.options());
+  out.seg_overflow = at::empty({F}, opts32);
+  // 2048-key tiles: a segment of up to 2048 needs no merge at all, and every
+  // merge run is a multiple of kMergeChunk
+  int items = capacity > kTileSize ? 8 : 2;
+  int base_tile = kTileThreads * items;
+  int tiles_per_seg = (int)((capacity + base_tile - 1) / base_tile);
+  int bag_len_hint = (int)std::max<int64_t>(capacity / B, 1);
+  at::Tensor keysA, valsA, keysB, valsB;
+  if (tiles_per_seg > 1) {
+    keysA = at::empty({n}, opts32);
+    valsA = at::empty({n}, opts32);
+  }
+  auto u32 = [](at::Tensor& t) {
+    return t.defined() ? reinterpret_cast<uint32_t*>(t.data_ptr<int32_t>()) : nullptr;
+  };
+#define PLAN_SORT_LAUNCH(ITEMS, DIRECT)                                                     \
+  hipLaunchKernelGGL((plan_tile_sort_kernel<ITEMS, DIRECT>), dim3((int)F * tiles_per_seg),  \
+                     dim3(kTileThreads), 0, stream, indices.data_ptr<int64_t>(),            \
+                     offsets.data_ptr<int64_t>(), feat_d_out.data_ptr<int64_t>(),           \
+                     feat_row_offset.data_ptr<int64_t>(), (int)B, tiles_per_seg,            \
+                     (int)end_bit, capacity, bag_len_hint, u32(keysA), u32(valsA),          \
+                     out.sorted64.data_ptr<int64_t>(), out.perm.data_ptr<int32_t>(),        \
+                     out.pos_row.data_ptr<int32_t>(), out.pos_col.data_ptr<int64_t>(),      \
+                     out.seg_overflow.data_ptr<int32_t>(), clear_ws, clear_n)
+  if (tiles_per_seg == 1) {
+    if (items == 8) PLAN_SORT_LAUNCH(8, true); else PLAN_SORT_LAUNCH(2, true);
+    return out;
+  }
+  if (items == 8) PLAN_SORT_LAUNCH(8, false); else PLAN_SORT_LAUNCH(2, false);
+#undef PLAN_SORT_LAUNCH
+  const int64_t sorted_len = static_cast<int64_t>(tiles_per_seg) * base_tile;
+  int chunks_per_seg = (int)(sorted_len / kMergeChunk);
+  if (sorted_len > 4 * (int64_t)base_tile) {
+    keysB = at::empty({n}, opts32);
+    valsB = at::empty({n}, opts32);
+  }
+  bool a_is_src = true;
+  for (int64_t run_len = base_tile; run_len < sorted_len; run_len *= 4) {
+    const bool last = run_len * 4 >= sorted_len;
+    const bool lds = run_len * 4 <= kMergeLdsKeys;
+    auto& src_k = a_is_src ? keysA : keysB;
+    auto& src_v = a_is_src ? valsA : valsB;
+    auto& dst_k = a_is_src ? keysB : keysA;
+    auto& dst_v = a_is_src ? valsB : valsA;
+#define PLAN_MERGE_LAUNCH(LDS, OUT64)                                                       \
+  hipLaunchKernelGGL((seg_merge4_kernel<LDS, OUT64>), dim3((int)F * chunks_per_seg),        \
+                     dim3(kTileThreads), 0, stream, u32(src_k), u32(src_v),                 \
+                     offsets.data_ptr<int64_t>(), (int)B, chunks_per_seg, (int)run_len,     \
+                     OUT64 ? nullptr : u32(dst_k),                                          \
+                     OUT64 ? out.sorted64.data_ptr<int64_t>() : nullptr,                    \
+                     OUT64 ? nullptr : u32(dst_v),                                          \
+                     OUT64 ? out.perm.data_ptr<int32_t>() : nullptr)
+    if (last) {
+      if (lds) PLAN_MERGE_LAUNCH(true, true); else PLAN_MERGE_LAUNCH(false, true);
+    } else {
+      if (lds) PLAN_MERGE_LAUNCH(true, false); else PLAN_MERGE_LAUNCH(false, false);
+    }
+#undef PLAN_MERGE_LAUNCH
+    a_is_src = !a_is_src;
+  }
+  return out;
+}
+}  // namespace
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> tbe_backward_plan_sort(
+    const at::Tensor& offsets, const at::Tensor& indices, const at::Tensor& feat_d_out,
+    const at::Tensor& feat_row_offset, int64_t B, int64_t F, int64_t end_bit,
+    int64_t capacity) {
+  if (indices.numel() == 0 || F == 0) {
+    auto opts32 = indices.options().dtype(at::kInt);
+    return {at::empty({0}, indices.options()), at::empty({0}, opts32),
+            at::empty({0}, opts32), at::empty({0}, indices.options()),
+            at::zeros({F}, opts32)};
+  }
+  auto s = plan_sort_launch(offsets, indices, feat_d_out, feat_row_offset, B, F, end_bit,
+                            capacity, nullptr, 0, tbe_stream());
+  return {s.sorted64, s.perm, s.pos_row, s.pos_col, s.seg_overflow};
+}
+
 std::tuple<at::Tensor, at::Tensor, at::Tensor> seg_sort_pairs_large(
     const at::Tensor& linear, const at::Tensor& feat_bounds /* [F+1] */, int64_t F,
     int64_t end_bit) {
@@ -1013,76 +1328,6 @@ std::tuple<at::Tensor, at::Tensor> tbe_backward_prep(const at::Tensor& sorted_li
 // atomics. Mirrors the reference's short/long-run split (triton TBE
 // :787/:1292) redesigned for wave-slot scheduling.
 // ---------------------------------------------------------------------------
-
-__global__ void __launch_bounds__(kBlockThreads) prep_chunks_lookback_kernel(
-    const int32_t* __restrict__ seg_offsets, const int32_t* __restrict__ num_runs_ptr,
-    int64_t n, int chunk_size, int32_t* __restrict__ chunk_offsets,
-    int32_t* __restrict__ total, uint64_t* __restrict__ tile_state,
-    int* __restrict__ tile_counter) {
-  using BlockScan = hipcub::BlockScan<int32_t, kBlockThreads>;
-  __shared__ typename BlockScan::TempStorage temp;
-  __shared__ int s_tile;
-  __shared__ int32_t s_prefix;
-  if (threadIdx.x == 0) s_tile = atomicAdd(tile_counter, 1);
-  __syncthreads();
-  const int tile = s_tile;
-  const int64_t base = static_cast<int64_t>(tile) * kScanTile;
-  const int32_t num_runs = *num_runs_ptr;
-  int32_t nc[kScanItems];
-  int32_t incl[kScanItems];
-#pragma unroll
-  for (int v = 0; v < kScanItems; ++v) {
-    int64_t r = base + static_cast<int64_t>(threadIdx.x) * kScanItems + v;
-    int32_t c = 0;
-    if (r < num_runs) {
-      int32_t len = seg_offsets[r + 1] - seg_offsets[r];
-      if (len > chunk_size) c = (len + chunk_size - 1) / chunk_size;
-    }
-    nc[v] = c;
-  }
-  int32_t agg;
-  BlockScan(temp).InclusiveSum(nc, incl, agg);
-  __syncthreads();
-  if (threadIdx.x < kWaveSize) {
-    if (threadIdx.x == 0) scan_publish(tile_state, tile, agg, 1);
-    int32_t pre = scan_lookback_wave(tile_state, tile, threadIdx.x);
-    if (threadIdx.x == 0) {
-      s_prefix = pre;
-      scan_publish(tile_state, tile, pre + agg, 2);
-    }
-  }
-  __syncthreads();
-  const int32_t prefix = s_prefix;
-#pragma unroll
-  for (int v = 0; v < kScanItems; ++v) {
-    int64_t r = base + static_cast<int64_t>(threadIdx.x) * kScanItems + v;
-    if (r < n) {
-      chunk_offsets[r + 1] = prefix + incl[v];
-      if (r == 0) chunk_offsets[0] = 0;
-      if (r == num_runs - 1) *total = prefix + incl[v];
-    }
-  }
-}
-
-std::tuple<at::Tensor, at::Tensor> tbe_backward_chunk_prep(const at::Tensor& seg_offsets,
-                                                           const at::Tensor& num_runs,
-                                                           int64_t chunk_size) {
-  int64_t n = seg_offsets.numel() - 1;  // max possible runs
-  auto opts = seg_offsets.options();
-  auto chunk_offsets = at::empty({n + 1}, opts);
-  auto total = at::empty({1}, opts);  // writer guaranteed: n>0 => num_runs>=1
-  if (n == 0) return {chunk_offsets, total.zero_()};
-  auto stream = tbe_stream();
-  int64_t tiles = (n + kScanTile - 1) / kScanTile;
-  auto ws = at::zeros({tiles + 1}, seg_offsets.options().dtype(at::kLong));
-  hipLaunchKernelGGL(prep_chunks_lookback_kernel, dim3((int)tiles), dim3(kBlockThreads),
-                     0, stream, seg_offsets.data_ptr<int32_t>(),
-                     num_runs.data_ptr<int32_t>(), n, (int)chunk_size,
-                     chunk_offsets.data_ptr<int32_t>(), total.data_ptr<int32_t>(),
-                     reinterpret_cast<uint64_t*>(ws.data_ptr<int64_t>()),
-                     reinterpret_cast<int*>(ws.data_ptr<int64_t>() + tiles));
-  return {chunk_offsets, total};
-}
 
 // third descriptor word of a run: where its first occurrence's grad row is
 // (a run of one occurrence goes from descriptor straight to the row) and D
@@ -1250,8 +1495,9 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_long_partial_kernel(
   }
 }
 
-// one streaming pass builds (a) a 48-byte descriptor per duplicate-index run
-// — collapsing the fused kernel's 7-deep dependent scalar chain
+// one kernel plans the chunks of the long runs and builds everything the two
+// gradient kernels read: (a) a 48-byte descriptor per duplicate-index run —
+// collapsing the fused kernel's 7-deep dependent scalar chain
 // (seg_offsets -> sorted_linear -> table binary search -> chunk_offsets) to
 // three independent vector loads — and (b) the grad-row offset (+ scale) per
 // SORTED position, so the gather chain perm -> (row, col) -> grad row
@@ -1260,72 +1506,183 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_bwd_long_partial_kernel(
 // nothing up. Measured motivation: with ids made fully sequential the fused
 // kernel only sped up 8% => it is latency-chain bound, not
 // DRAM-randomness bound.
-__global__ void __launch_bounds__(kBlockThreads) tbe_bwd_build_desc_kernel(
-    const int32_t* __restrict__ seg_offsets, const int32_t* __restrict__ chunk_offsets,
-    const int32_t* __restrict__ num_runs_ptr, const int64_t* __restrict__ sorted_linear,
-    const int32_t* __restrict__ sort_perm, const int32_t* __restrict__ pos_row,
-    const int64_t* __restrict__ pos_col, const float* __restrict__ pos_scale,
-    int64_t grad_stride, const int64_t* __restrict__ table_row_offsets,
+//
+// A tile is kPlanTile positions and the kPlanTile runs of the same indices
+// (runs <= n). The chunk counts of the runs go through a block scan and the
+// decoupled lookback; each thread then holds c0 and c1 of its own runs, so
+// chunk_offsets is never materialised. The tile publishes its aggregate as
+// soon as the block scan has it; everything that does not need the prefix
+// (the per-position half, desc_b, desc_c) runs between that and the lookback,
+// so the lookback finds its predecessors published. Loads go to clamped,
+// always-valid indices and only the stores are guarded: each phase then has
+// the loads of all kPlanItems items in flight at once instead of one
+// dependent chain per item. tile_state / tile_counter must have been zeroed
+// by a fill or a kernel earlier on the same stream in the same call.
+constexpr int kPlanItems = 4;
+constexpr int kPlanTile = kBlockThreads * kPlanItems;
+
+__global__ void __launch_bounds__(kBlockThreads) plan_chunks_desc_kernel(
+    const int32_t* __restrict__ seg_offsets, const int32_t* __restrict__ num_runs_ptr,
+    const int64_t* __restrict__ sorted_linear, const int32_t* __restrict__ sort_perm,
+    const int32_t* __restrict__ pos_row, const int64_t* __restrict__ pos_col,
+    const float* __restrict__ pos_scale, int64_t grad_stride,
+    const int64_t* __restrict__ table_row_offsets,
     const int64_t* __restrict__ table_elem_offsets, const int32_t* __restrict__ dims,
     int T, int64_t n, int chunk_size, int4* __restrict__ desc_a,
     longlong2* __restrict__ desc_b, RunHead* __restrict__ desc_c,
     int4* __restrict__ chunk_desc, int64_t* __restrict__ grow_off,
-    float* __restrict__ sorted_scale) {
+    float* __restrict__ sorted_scale, int32_t* __restrict__ total,
+    uint64_t* __restrict__ tile_state, int* __restrict__ tile_counter) {
   // a run of more chunks than this has its chunk descriptors written by the
   // whole wave, not by its own thread (the 3-row table: 683 chunks at B=65536)
   constexpr int kOwnChunks = 16;
-  int32_t num_runs = *num_runs_ptr;
+  using BlockScan = hipcub::BlockScan<int32_t, kBlockThreads>;
+  __shared__ typename BlockScan::TempStorage temp;
+  __shared__ int s_tile;
+  __shared__ int32_t s_prefix;
+  if (threadIdx.x == 0) s_tile = atomicAdd(tile_counter, 1);
+  __syncthreads();
+  const int tile = s_tile;
+  const int64_t base = static_cast<int64_t>(tile) * kPlanTile;
+  const int32_t num_runs = *num_runs_ptr;  // >= 1 as n > 0
   const int lane = threadIdx.x & (kWaveSize - 1);
-  // the loop is wave-uniform (base is lane 0's index) so that the ballot
-  // below sees every lane of the wave
-  for (int64_t base = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x - lane;
-       base < n; base += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    const int64_t i = base + lane;
-    if (i < n) {
-      int32_t p = sort_perm[i];
-      grow_off[i] = static_cast<int64_t>(pos_row[p]) * grad_stride + pos_col[p];
-      if (sorted_scale) sorted_scale[i] = pos_scale[p];
+  // per-run half: blocked, as the scan wants it. A thread past the last run
+  // reads run 0 and counts nothing.
+  int32_t k0[kPlanItems], k1[kPlanItems], nc[kPlanItems], incl[kPlanItems];
+  bool live[kPlanItems];
+  const int64_t r0 = base + static_cast<int64_t>(threadIdx.x) * kPlanItems;
+#pragma unroll
+  for (int v = 0; v < kPlanItems; ++v) {
+    live[v] = r0 + v < num_runs;
+    const int64_t rc = live[v] ? r0 + v : 0;
+    k0[v] = seg_offsets[rc];
+    k1[v] = seg_offsets[rc + 1];
+  }
+#pragma unroll
+  for (int v = 0; v < kPlanItems; ++v) {
+    const int32_t len = k1[v] - k0[v];
+    nc[v] = (live[v] && len > chunk_size) ? (len + chunk_size - 1) / chunk_size : 0;
+  }
+  int32_t agg;
+  BlockScan(temp).InclusiveSum(nc, incl, agg);
+  if (threadIdx.x == 0) scan_publish(tile_state, tile, agg, 1);
+
+  // per-position half: striped, so a wave reads and writes whole lines
+  {
+    int32_t p[kPlanItems];
+    int32_t pr[kPlanItems];
+    int64_t pc[kPlanItems];
+    float ps[kPlanItems];
+#pragma unroll
+    for (int v = 0; v < kPlanItems; ++v) {
+      const int64_t i = base + v * kBlockThreads + threadIdx.x;
+      p[v] = sort_perm[min(i, n - 1)];
     }
-    int32_t k0 = 0, k1 = 0, c0 = 0, nch = 0;
-    int D = 0;
-    if (i < num_runs) {
-      k0 = seg_offsets[i];
-      k1 = seg_offsets[i + 1];
-      int64_t lin = sorted_linear[k0];
-      int32_t p0 = sort_perm[k0];
-      int t = upper_bound_segment(table_row_offsets, T, lin);
-      D = dims[t];
-      c0 = chunk_offsets[i];
-      int32_t c1 = chunk_offsets[i + 1];
-      nch = c1 - c0;
-      desc_a[i] = make_int4(k0, k1, c0, c1);
-      longlong2 b;
-      b.x = lin;
-      b.y = table_elem_offsets[t] + (lin - table_row_offsets[t]) * static_cast<int64_t>(D);
-      desc_b[i] = b;
-      RunHead h;
-      h.first_off = static_cast<int64_t>(pos_row[p0]) * grad_stride + pos_col[p0];
-      h.D = D;
-      h.first_scale = pos_scale ? pos_scale[p0] : 1.f;
-      desc_c[i] = h;
-      if (nch <= kOwnChunks) {
-        for (int j = 0; j < nch; ++j) {
-          int32_t ck = k0 + j * chunk_size;
-          chunk_desc[c0 + j] = make_int4(ck, min(k1, ck + chunk_size), D, (int)i);
+#pragma unroll
+    for (int v = 0; v < kPlanItems; ++v) {
+      pr[v] = pos_row[p[v]];
+      pc[v] = pos_col[p[v]];
+      ps[v] = sorted_scale ? pos_scale[p[v]] : 1.f;
+    }
+#pragma unroll
+    for (int v = 0; v < kPlanItems; ++v) {
+      const int64_t i = base + v * kBlockThreads + threadIdx.x;
+      if (i < n) {
+        grow_off[i] = static_cast<int64_t>(pr[v]) * grad_stride + pc[v];
+        if (sorted_scale) sorted_scale[i] = ps[v];
+      }
+    }
+  }
+  // run heads: desc_b and desc_c need no prefix
+  int32_t D[kPlanItems];
+  {
+    int64_t lin[kPlanItems];
+    int32_t p0[kPlanItems];
+    int tlo[kPlanItems], thi[kPlanItems];
+#pragma unroll
+    for (int v = 0; v < kPlanItems; ++v) {
+      lin[v] = sorted_linear[k0[v]];
+      p0[v] = sort_perm[k0[v]];
+      tlo[v] = 0;
+      thi[v] = T;
+    }
+    // upper_bound_segment(table_row_offsets, T, lin) for all items in step
+    for (bool go = T > 1; go;) {
+      go = false;
+#pragma unroll
+      for (int v = 0; v < kPlanItems; ++v) {
+        const bool act = thi[v] - tlo[v] > 1;
+        const int mid = (tlo[v] + thi[v]) >> 1;
+        const bool le = table_row_offsets[mid] <= lin[v];
+        tlo[v] = (act && le) ? mid : tlo[v];
+        thi[v] = (act && !le) ? mid : thi[v];
+        go |= thi[v] - tlo[v] > 1;
+      }
+    }
+    int64_t te[kPlanItems], tr[kPlanItems], hc[kPlanItems];
+    int32_t hr[kPlanItems];
+    float hs[kPlanItems];
+#pragma unroll
+    for (int v = 0; v < kPlanItems; ++v) {
+      const int t = tlo[v];
+      D[v] = dims[t];
+      te[v] = table_elem_offsets[t];
+      tr[v] = table_row_offsets[t];
+      hr[v] = pos_row[p0[v]];
+      hc[v] = pos_col[p0[v]];
+      hs[v] = pos_scale ? pos_scale[p0[v]] : 1.f;
+    }
+#pragma unroll
+    for (int v = 0; v < kPlanItems; ++v) {
+      if (live[v]) {
+        longlong2 b;
+        b.x = lin[v];
+        b.y = te[v] + (lin[v] - tr[v]) * static_cast<int64_t>(D[v]);
+        desc_b[r0 + v] = b;
+        RunHead h;
+        h.first_off = static_cast<int64_t>(hr[v]) * grad_stride + hc[v];
+        h.D = D[v];
+        h.first_scale = hs[v];
+        desc_c[r0 + v] = h;
+      }
+    }
+  }
+  if (threadIdx.x < kWaveSize) {
+    int32_t pre = scan_lookback_wave(tile_state, tile, threadIdx.x);
+    if (threadIdx.x == 0) {
+      s_prefix = pre;
+      scan_publish(tile_state, tile, pre + agg, 2);
+    }
+  }
+  __syncthreads();
+  const int32_t prefix = s_prefix;
+  // the v loop is wave-uniform so that the ballot sees every lane of the wave
+#pragma unroll
+  for (int v = 0; v < kPlanItems; ++v) {
+    const int64_t r = r0 + v;
+    const int32_t c1 = prefix + incl[v];
+    const int32_t c0 = c1 - nc[v];
+    if (live[v]) {
+      desc_a[r] = make_int4(k0[v], k1[v], c0, c1);
+      if (r == num_runs - 1) *total = c1;
+      if (nc[v] <= kOwnChunks) {
+        for (int j = 0; j < nc[v]; ++j) {
+          int32_t ck = k0[v] + j * chunk_size;
+          chunk_desc[c0 + j] = make_int4(ck, min(k1[v], ck + chunk_size), D[v], (int)r);
         }
       }
     }
-    uint64_t wide = __ballot(nch > kOwnChunks);
+    uint64_t wide = __ballot(nc[v] > kOwnChunks);
     while (wide) {
       const int src = __ffsll(static_cast<unsigned long long>(wide)) - 1;
       wide &= wide - 1;
-      const int32_t sk0 = __shfl(k0, src, kWaveSize), sk1 = __shfl(k1, src, kWaveSize);
-      const int32_t sc0 = __shfl(c0, src, kWaveSize), sn = __shfl(nch, src, kWaveSize);
-      const int sD = __shfl(D, src, kWaveSize);
+      const int32_t sk0 = __shfl(k0[v], src, kWaveSize), sk1 = __shfl(k1[v], src, kWaveSize);
+      const int32_t sc0 = __shfl(c0, src, kWaveSize), sn = __shfl(nc[v], src, kWaveSize);
+      const int sD = __shfl(D[v], src, kWaveSize);
+      const int srun = static_cast<int>(r) + (src - lane) * kPlanItems;
       for (int j = lane; j < sn; j += kWaveSize) {
         int32_t ck = sk0 + j * chunk_size;
-        chunk_desc[sc0 + j] =
-            make_int4(ck, min(sk1, ck + chunk_size), sD, (int)(base + src));
+        chunk_desc[sc0 + j] = make_int4(ck, min(sk1, ck + chunk_size), sD, srun);
       }
     }
   }
@@ -1557,7 +1914,7 @@ static void launch_tbe_bwd(
     at::Tensor& weights, at::Tensor& momentum, const at::Tensor& grad,
     const at::Tensor& sorted_linear, const at::Tensor& sort_perm,
     const at::Tensor& seg_offsets, const at::Tensor& num_runs,
-    const at::Tensor& chunk_offsets, const at::Tensor& total_chunks,
+    uint64_t* chunk_ws, const at::Tensor& total_chunks,
     const at::Tensor& scratch, const at::Tensor& pos_row, const at::Tensor& pos_col,
     const float* scale_ptr, const at::Tensor& table_row_offsets,
     const at::Tensor& table_elem_offsets, const at::Tensor& dims, int T,
@@ -1569,8 +1926,10 @@ static void launch_tbe_bwd(
   const g_t* grad_ptr = reinterpret_cast<const g_t*>(grad.data_ptr());
   emb_t* gw_ptr = grad_weights.numel() > 0
       ? reinterpret_cast<emb_t*>(grad_weights.data_ptr<host_w_t>()) : nullptr;
-  // one streaming pass collapses the per-run metadata chain + per-position
-  // grad gather chain (see tbe_bwd_build_desc_kernel)
+  // one pass plans the chunks and collapses the per-run metadata chain + the
+  // per-position grad gather chain (see plan_chunks_desc_kernel). chunk_ws is
+  // that kernel's lookback workspace, [tiles] states + 1 counter, already
+  // zeroed on this stream by the caller
   int64_t n = sorted_linear.numel();
   auto opts_i = sorted_linear.options().dtype(at::kInt);
   auto desc_a_t = at::empty({n * 4}, opts_i);
@@ -1589,16 +1948,17 @@ static void launch_tbe_bwd(
   longlong2* desc_b_p = reinterpret_cast<longlong2*>(desc_b_t.data_ptr<int64_t>());
   RunHead* desc_c_p = reinterpret_cast<RunHead*>(desc_c_t.data_ptr<int64_t>());
   int4* chunk_desc_p = reinterpret_cast<int4*>(chunk_desc_t.data_ptr<int32_t>());
-  hipLaunchKernelGGL(tbe_bwd_build_desc_kernel, dim3(grid_for(n, kBlockThreads)),
-                     dim3(kBlockThreads), 0, stream,
-                     seg_offsets.data_ptr<int32_t>(), chunk_offsets.data_ptr<int32_t>(),
-                     num_runs.data_ptr<int32_t>(), sorted_linear.data_ptr<int64_t>(),
-                     sort_perm.data_ptr<int32_t>(), pos_row.data_ptr<int32_t>(),
-                     pos_col.data_ptr<int64_t>(), scale_ptr, grad.size(1),
-                     table_row_offsets.data_ptr<int64_t>(),
+  const int64_t tiles = (n + kPlanTile - 1) / kPlanTile;
+  hipLaunchKernelGGL(plan_chunks_desc_kernel, dim3((int)tiles), dim3(kBlockThreads), 0,
+                     stream, seg_offsets.data_ptr<int32_t>(), num_runs.data_ptr<int32_t>(),
+                     sorted_linear.data_ptr<int64_t>(), sort_perm.data_ptr<int32_t>(),
+                     pos_row.data_ptr<int32_t>(), pos_col.data_ptr<int64_t>(), scale_ptr,
+                     grad.size(1), table_row_offsets.data_ptr<int64_t>(),
                      table_elem_offsets.data_ptr<int64_t>(), dims.data_ptr<int32_t>(), T,
                      n, chunk_size, desc_a_p, desc_b_p, desc_c_p, chunk_desc_p,
-                     grow_off_t.data_ptr<int64_t>(), sscale_ptr);
+                     grow_off_t.data_ptr<int64_t>(), sscale_ptr,
+                     total_chunks.data_ptr<int32_t>(), chunk_ws,
+                     reinterpret_cast<int*>(chunk_ws + tiles));
 #define TBE_BWD_FUSED(LPS, CHUNKS, ADAM)                                                      \
   hipLaunchKernelGGL((tbe_bwd_fused_kernel<emb_t, g_t, LPS, CHUNKS, ADAM>), dim3(grid),      \
                      dim3(kBlockThreads),                                                    \
@@ -1636,7 +1996,7 @@ template <typename emb_t, typename host_w_t>
 static void dispatch_tbe_bwd_grad(const at::ScalarType g_st, at::Tensor& weights,
     at::Tensor& momentum, const at::Tensor& grad, const at::Tensor& sorted_linear,
     const at::Tensor& sort_perm, const at::Tensor& seg_offsets, const at::Tensor& num_runs,
-    const at::Tensor& chunk_offsets, const at::Tensor& total_chunks,
+    uint64_t* chunk_ws, const at::Tensor& total_chunks,
     const at::Tensor& scratch, const at::Tensor& pos_row, const at::Tensor& pos_col,
     const float* scale_ptr, const at::Tensor& table_row_offsets,
     const at::Tensor& table_elem_offsets, const at::Tensor& dims, int T, int chunk_size,
@@ -1646,7 +2006,7 @@ static void dispatch_tbe_bwd_grad(const at::ScalarType g_st, at::Tensor& weights
     const int64_t* rng_ptr, int stochastic, int lps, int chunks, int grid,
     int grid_long, hipStream_t stream) {
 #define ARGS weights, momentum, grad, sorted_linear, sort_perm, seg_offsets, num_runs,  \
-    chunk_offsets, total_chunks, scratch, pos_row, pos_col, scale_ptr,                  \
+    chunk_ws, total_chunks, scratch, pos_row, pos_col, scale_ptr,                  \
     table_row_offsets, table_elem_offsets, dims, T, chunk_size, max_D, lr, eps, mode,   \
     grad_weights, cache_w_ptr, cache_loc_ptr, m1_ptr, m2_ptr, beta1, beta2, iter_ptr,   \
     rng_ptr, stochastic, lps, chunks, grid, grid_long, stream
@@ -1657,7 +2017,12 @@ static void dispatch_tbe_bwd_grad(const at::ScalarType g_st, at::Tensor& weights
 #undef ARGS
 }
 
-void tbe_backward_fused(
+// chunk_ws: the chunk scan's lookback workspace, plan_ws_words(n) 64-bit
+// words that a fill or a kernel earlier on this stream, in this call, zeroed
+static int64_t plan_ws_words(int64_t n) { return (n + kPlanTile - 1) / kPlanTile + 1; }
+static int64_t runs_ws_words(int64_t n) { return (n + kScanTile - 1) / kScanTile + 1; }
+
+static void tbe_backward_fused_ws(
     at::Tensor weights, at::Tensor momentum, const at::Tensor& grad,
     const at::Tensor& sorted_linear, const at::Tensor& sort_perm,
     const at::Tensor& seg_offsets, const at::Tensor& num_runs, const at::Tensor& pos_row,
@@ -1666,9 +2031,9 @@ void tbe_backward_fused(
     const at::Tensor& dims, int64_t max_D, double lr, double eps, int64_t mode,
     at::Tensor grad_weights, at::Tensor cache_weights, const at::Tensor& cache_loc,
     at::Tensor m1, at::Tensor m2, double beta1, double beta2,
-    const at::Tensor& iter_t, const at::Tensor& rng_state, bool stochastic) {
+    const at::Tensor& iter_t, const at::Tensor& rng_state, bool stochastic,
+    uint64_t* chunk_ws) {
   int64_t n = sorted_linear.numel();
-  if (n == 0) return;
   int T = table_elem_offsets.numel();
   auto stream = tbe_stream();
   int lps = (max_D <= 64) ? 16 : (max_D <= 128 ? 32 : 64);
@@ -1687,7 +2052,8 @@ void tbe_backward_fused(
 
   // chunk long duplicate-runs: partials scratch sized by the host upper bound
   constexpr int kChunkSize = 32;
-  auto [chunk_offsets, total_chunks] = tbe_backward_chunk_prep(seg_offsets, num_runs, kChunkSize);
+  // written by the run num_runs - 1 (n > 0 => num_runs >= 1)
+  auto total_chunks = at::empty({1}, seg_offsets.options());
   int64_t max_chunks = 2 * ((n + kChunkSize - 1) / kChunkSize) + 2;
   auto scratch = at::empty({max_chunks * max_D}, grad.options().dtype(at::kFloat));
   int grid_long = grid_for(max_chunks * lps, kBlockThreads);
@@ -1698,7 +2064,7 @@ void tbe_backward_fused(
   const int64_t* rng_ptr =
       rng_state.numel() > 0 ? rng_state.data_ptr<int64_t>() : nullptr;
 #define BARGS weights, momentum, grad, sorted_linear, sort_perm, seg_offsets, num_runs, \
-    chunk_offsets, total_chunks, scratch, pos_row, pos_col, scale_ptr,                  \
+    chunk_ws, total_chunks, scratch, pos_row, pos_col, scale_ptr,                  \
     table_row_offsets, table_elem_offsets, dims, T, kChunkSize, max_D, (float)lr,       \
     (float)eps, (int)mode, grad_weights, cache_w_ptr, cache_loc_ptr, m1_ptr, m2_ptr,    \
     (float)beta1, (float)beta2, iter_ptr, rng_ptr, stochastic ? 1 : 0, lps, chunks,     \
@@ -1711,6 +2077,66 @@ void tbe_backward_fused(
   else if (w_st == at::kHalf) dispatch_tbe_bwd_grad<__half, at::Half>(g_st, BARGS);
   else TORCH_CHECK(false, "unsupported TBE weights dtype");
 #undef BARGS
+}
+
+void tbe_backward_fused(
+    at::Tensor weights, at::Tensor momentum, const at::Tensor& grad,
+    const at::Tensor& sorted_linear, const at::Tensor& sort_perm,
+    const at::Tensor& seg_offsets, const at::Tensor& num_runs, const at::Tensor& pos_row,
+    const at::Tensor& pos_col, const at::Tensor& pos_scale,
+    const at::Tensor& table_row_offsets, const at::Tensor& table_elem_offsets,
+    const at::Tensor& dims, int64_t max_D, double lr, double eps, int64_t mode,
+    at::Tensor grad_weights, at::Tensor cache_weights, const at::Tensor& cache_loc,
+    at::Tensor m1, at::Tensor m2, double beta1, double beta2,
+    const at::Tensor& iter_t, const at::Tensor& rng_state, bool stochastic) {
+  int64_t n = sorted_linear.numel();
+  if (n == 0) return;
+  // stand-alone: nothing earlier in this call can clear the workspace
+  auto ws = at::zeros({plan_ws_words(n)}, sorted_linear.options());
+  tbe_backward_fused_ws(weights, momentum, grad, sorted_linear, sort_perm, seg_offsets,
+                        num_runs, pos_row, pos_col, pos_scale, table_row_offsets,
+                        table_elem_offsets, dims, max_D, lr, eps, mode, grad_weights,
+                        cache_weights, cache_loc, m1, m2, beta1, beta2, iter_t, rng_state,
+                        stochastic, reinterpret_cast<uint64_t*>(ws.data_ptr<int64_t>()));
+}
+
+// The whole backward of the fixed-bag-length, table-ordered case as one plan:
+// sort+metadata -> merge round(s) -> run scan -> chunk scan+descriptors ->
+// long-partial -> fused update. Both lookback workspaces are allocated before
+// the chain starts and zeroed by its first kernel, so the chain has no fill;
+// as that kernel is part of every call and of every graph replay, neither
+// scan ever starts on a workspace that was not cleared before it. Returns the
+// per-segment overflow flags (segment longer than the capacity).
+at::Tensor tbe_backward_planned(
+    at::Tensor weights, at::Tensor momentum, const at::Tensor& grad,
+    const at::Tensor& indices, const at::Tensor& offsets, const at::Tensor& feat_d_out,
+    const at::Tensor& feat_row_offset, int64_t B, int64_t F, int64_t end_bit,
+    int64_t capacity, const at::Tensor& pos_scale, const at::Tensor& table_row_offsets,
+    const at::Tensor& table_elem_offsets, const at::Tensor& dims, int64_t max_D, double lr,
+    double eps, int64_t mode, at::Tensor grad_weights, at::Tensor cache_weights,
+    const at::Tensor& cache_loc, at::Tensor m1, at::Tensor m2, double beta1, double beta2,
+    const at::Tensor& iter_t, const at::Tensor& rng_state, bool stochastic) {
+  int64_t n = indices.numel();
+  auto opts32 = indices.options().dtype(at::kInt);
+  if (n == 0 || F == 0) return at::zeros({F}, opts32);
+  auto stream = tbe_stream();
+  const int64_t words = runs_ws_words(n);
+  auto ws = at::empty({words + plan_ws_words(n)}, indices.options());
+  uint64_t* runs_ws = reinterpret_cast<uint64_t*>(ws.data_ptr<int64_t>());
+  auto s = plan_sort_launch(offsets, indices, feat_d_out, feat_row_offset, B, F, end_bit,
+                            capacity, runs_ws, (int)ws.numel(), stream);
+  auto seg_offsets = at::empty({n + 1}, opts32);
+  auto num_runs = at::empty({1}, opts32);
+  hipLaunchKernelGGL(prep_runs_lookback_kernel, dim3((int)(words - 1)), dim3(kBlockThreads),
+                     0, stream, s.sorted64.data_ptr<int64_t>(), n,
+                     seg_offsets.data_ptr<int32_t>(), num_runs.data_ptr<int32_t>(), runs_ws,
+                     reinterpret_cast<int*>(runs_ws + (words - 1)));
+  tbe_backward_fused_ws(weights, momentum, grad, s.sorted64, s.perm, seg_offsets, num_runs,
+                        s.pos_row, s.pos_col, pos_scale, table_row_offsets,
+                        table_elem_offsets, dims, max_D, lr, eps, mode, grad_weights,
+                        cache_weights, cache_loc, m1, m2, beta1, beta2, iter_t, rng_state,
+                        stochastic, runs_ws + words);
+  return s.seg_overflow;
 }
 
 __global__ void gather_run_heads_kernel(const int64_t* __restrict__ sorted_lin,

@@ -497,6 +497,58 @@ class TableBatchedEmbeddingBags(nn.Module):
         need_bags = self.pooling_mode == PoolingMode.MEAN or (
             psw is not None and psw.requires_grad
         )
+        cap = (self.fixed_bag_length or 0) * B
+        if (
+            indices.is_cuda
+            and not need_bags
+            and self._seg_sort_ok
+            and 0 < cap
+            and indices.numel() <= cap * self._num_features
+            and os.environ.get("TREC_SEG_SORT", "1") not in ("0", "block")
+            and os.environ.get("TREC_BWD_PLAN", "1") != "0"
+        ):
+            # the whole index-only prep chain and the update as one planned
+            # op: four prep kernels, no fill (TREC_BWD_PLAN=0 keeps the
+            # op-by-op chain below)
+            self._pre_update()
+            seg_overflow = torch.ops.trec_amd.tbe_backward_planned(
+                self.weights if not isinstance(self.weights, nn.Parameter) else self.weights.data,
+                self.momentum,
+                grad,
+                indices,
+                offsets,
+                self._feat_d_out,
+                self._feat_row_offset,
+                B,
+                self._num_features,
+                _bits_needed(self._total_rows),
+                cap,
+                psw if psw is not None else self._empty_f,
+                self._table_row_offsets,
+                self._table_elem_offsets,
+                self._dims_t,
+                self._max_D,
+                self.learning_rate,
+                self.eps,
+                self.optimizer if mode is None else mode,
+                grad_weights if grad_weights is not None else self._empty_f,
+                self.cache_weights,
+                cache_loc if cache_loc is not None else self._empty_i,
+                self.m1,
+                self.m2,
+                self.beta1,
+                self.beta2,
+                self._iter,
+                self._rng,
+                self.stochastic_rounding,
+            )
+            if os.environ.get("TREC_DEBUG") == "1" and bool(seg_overflow.any().item()):
+                raise RuntimeError(
+                    "TBE segmented sort overflow: a bag exceeded "
+                    f"fixed_bag_length={self.fixed_bag_length}; tail gradients "
+                    "would be dropped. Remove fixed_bag_length or raise it."
+                )
+            return None
         pos_row, pos_col, linear, bag_ids = self._bag_metadata(
             indices, offsets, B, need_bag_ids=need_bags
         )
