@@ -134,6 +134,126 @@ def test_prefetch_pipeline_uvm_caching_cuda():
     torch.cuda.synchronize()
 
 
+def test_prefetch_pipeline_uvm_caching_matches_fused():
+    """The prefetch pipeline over a one-set lxu cache computes what it computes
+    over HBM-resident tables: per-step losses and final tables. Every prefetch
+    displaces rows of the batch about to run (pre-condition checked on the CPU
+    in test_lxu_cache.TestPreconditionsD)."""
+    import bench
+    import numpy as np
+
+    from tests.test_lxu_cache import PIPE_B, PIPE_ROWS, pipeline_ids
+    from torchrec_amd.datasets.random import Batch
+    from torchrec_amd.distributed.embeddingbag import EmbeddingBagCollectionSharder
+    from torchrec_amd.distributed.model_parallel import DistributedModelParallel
+    from torchrec_amd.distributed.planner.planners import EmbeddingShardingPlanner
+    from torchrec_amd.distributed.planner.types import ParameterConstraints, Topology
+    from torchrec_amd.distributed.train_pipeline import PrefetchTrainPipelineSparseDist
+    from torchrec_amd.distributed.types import ShardingEnv, ShardingType
+    from torchrec_amd.modules.embedding_configs import EmbeddingBagConfig
+    from torchrec_amd.modules.embedding_modules import EmbeddingBagCollection
+    from torchrec_amd.sparse.jagged_tensor import KeyedJaggedTensor
+
+    device = torch.device("cuda", 0)
+    D = 64
+    names = ["t0", "t1"]
+
+    class Tiny(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.ebc = EmbeddingBagCollection(
+                tables=[
+                    EmbeddingBagConfig(
+                        num_embeddings=r, embedding_dim=D, name=n, feature_names=[f"f_{n}"]
+                    )
+                    for n, r in zip(names, PIPE_ROWS)
+                ]
+            )
+            self.dense = torch.nn.Linear(len(names) * D, 1)
+
+        def forward(self, batch):
+            pooled = self.ebc(batch.sparse_features).values()
+            logits = self.dense(pooled).squeeze(1)
+            loss = torch.nn.functional.binary_cross_entropy_with_logits(
+                logits, batch.labels.float()
+            )
+            return loss, (loss.detach(), logits.detach())
+
+    g = torch.Generator().manual_seed(11)
+    init = {n: torch.randn(r, D, generator=g) for n, r in zip(names, PIPE_ROWS)}
+    batches = []
+    for k in range(4):
+        ids = pipeline_ids(k)
+        batches.append(
+            Batch(
+                dense_features=torch.zeros(PIPE_B, 1),
+                sparse_features=KeyedJaggedTensor(
+                    keys=[f"f_{n}" for n in names],
+                    values=torch.from_numpy(np.concatenate(ids)),
+                    lengths=torch.ones(len(names) * PIPE_B, dtype=torch.int64),
+                    stride=PIPE_B,
+                ),
+                labels=torch.randint(0, 2, (PIPE_B,), generator=g),
+            ).pin_memory()
+        )
+
+    def run(kernel):
+        torch.manual_seed(7)
+        model = Tiny()
+        sharder = EmbeddingBagCollectionSharder(
+            fused_params={"optimizer": "rowwise_adagrad", "learning_rate": 0.05,
+                          "cache_load_factor": 0.2}
+        )
+        constraints = {
+            n: ParameterConstraints(
+                sharding_types=[ShardingType.TABLE_WISE.value], compute_kernels=[kernel]
+            )
+            for n in names
+        }
+        planner = EmbeddingShardingPlanner(
+            topology=Topology(world_size=1, compute_device="cuda", batch_size=PIPE_B),
+            constraints=constraints,
+        )
+        plan = planner.plan(model, [sharder])
+        assert {ps.compute_kernel for mp in plan.plan.values() for ps in mp.values()} == {kernel}
+        dmp = DistributedModelParallel(
+            model, env=ShardingEnv.from_local(1, 0), plan=plan, sharders=[sharder], device=device
+        )
+        tbes = [t for sm in dmp.sharded_modules().values() for t in sm.tbes()]
+        assert sorted(s.name for t in tbes for s in t.embedding_specs) == names
+        for t in tbes:
+            if kernel == "fused_uvm_caching":
+                assert t._uvm_caching and t._cache_sets == 1 and t.cache_tags.numel() == 32
+            for spec, w in zip(t.embedding_specs, t.split_embedding_weights()):
+                w.copy_(init[spec.name])
+        opt = torch.optim.SGD([p for p in dmp.parameters() if p.requires_grad], lr=0.05)
+        pipe = PrefetchTrainPipelineSparseDist(dmp, opt, device)
+        it = bench._CyclingIterator(batches)
+        losses = [float(pipe.progress(it)[0]) for _ in range(6)]
+        torch.cuda.synchronize()
+        tables = {
+            spec.name: w.detach().cpu().clone()
+            for t in tbes
+            for spec, w in zip(t.embedding_specs, t.split_embedding_weights())
+        }
+        momentum = {
+            spec.name: st[0].detach().cpu().clone()
+            for t in tbes
+            for spec, st in zip(t.embedding_specs, t.split_optimizer_states())
+        }
+        return losses, tables, momentum
+
+    losses_c, tables_c, mom_c = run("fused_uvm_caching")
+    losses_f, tables_f, mom_f = run("fused")
+    print("losses cached:", losses_c, "fused:", losses_f)
+    torch.testing.assert_close(
+        torch.tensor(losses_c), torch.tensor(losses_f), atol=1e-4, rtol=1e-4
+    )
+    for n in names:
+        torch.testing.assert_close(tables_c[n], tables_f[n], atol=1e-5, rtol=1e-4, msg=lambda s: f"{n}: {s}")
+        torch.testing.assert_close(mom_c[n], mom_f[n], atol=1e-6, rtol=0)
+
+
 def test_sharded_ec_cuda():
     """Sequence EC under DMP on cuda:0 (native seq TBE path)."""
     from torchrec_amd.distributed.embedding import EmbeddingCollectionSharder

@@ -432,8 +432,16 @@ class PrefetchTrainPipelineSparseDist(TrainPipelineSparseDist):
         self._prefetched_dist: List[Dict[str, Tuple[Any, Any]]] = []
 
     def _prefetch(self, dists: Dict[str, Tuple[Any, Any]]) -> Dict[str, Tuple[Any, Any]]:
-        """Wait the batch's input_dist and run cache prefetch on its stream."""
+        """Wait the batch's input_dist and run cache prefetch on its stream.
+
+        The prefetch evicts and writes back rows that the previous batch's
+        backward updated on the default stream, so the prefetch stream first
+        waits for the default stream (and for the data-dist stream that made
+        the batch's ids)."""
         out: Dict[str, Tuple[Any, Any]] = {}
+        if self._prefetch_stream is not None:
+            self._prefetch_stream.wait_stream(torch.cuda.current_stream())
+            self._prefetch_stream.wait_stream(self._data_dist_stream)
         ctxmgr = (
             torch.cuda.stream(self._prefetch_stream)
             if self._prefetch_stream is not None
@@ -443,16 +451,28 @@ class PrefetchTrainPipelineSparseDist(TrainPipelineSparseDist):
             for fqn, (ctx, tensors_aw) in dists.items():
                 dist_input = tensors_aw.wait()
                 module = self._pipelined[fqn]
-                for lookup in getattr(module, "_lookups", []):
-                    kjts = (
-                        dist_input
-                        if isinstance(dist_input, list)
-                        else [dist_input]
-                    )
-                    for kjt, tbe_list in zip(kjts, [lookup.tbes()]):
-                        for tbe in tbe_list:
-                            if getattr(tbe, "_uvm_caching", False):
-                                tbe.prefetch(kjt.values(), kjt.offsets())
+                kjts = dist_input if isinstance(dist_input, list) else [dist_input]
+                # one KJT per lookup; a lookup with several TBE groups splits
+                # its KJT by feature exactly as its forward does
+                for lookup, kjt in zip(getattr(module, "_lookups", []), kjts):
+                    tbes = lookup.tbes()
+                    if not any(getattr(t, "_uvm_caching", False) for t in tbes):
+                        continue
+                    parts = [kjt] if len(tbes) == 1 else kjt.split(lookup._feature_splits)
+                    for part, tbe in zip(parts, tbes):
+                        if not getattr(tbe, "_uvm_caching", False):
+                            continue
+                        values, offsets = part.values(), part.offsets()
+                        if self._prefetch_stream is not None:
+                            # made on another stream, read on this one
+                            values.record_stream(self._prefetch_stream)
+                            offsets.record_stream(self._prefetch_stream)
+                        bpf = (
+                            [sum(sp) for sp in part.stride_per_key_per_rank()]
+                            if part.variable_stride_per_key()
+                            else None
+                        )
+                        tbe.prefetch(values, offsets, bpf)
                 out[fqn] = (ctx, _Ready(dist_input))
         return out
 

@@ -74,7 +74,10 @@ class _TBEPooledFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dummy, host, indices, offsets, psw):  # type: ignore[override]
-        cache_loc = host._prefetch_cache(indices, offsets)
+        # cached modules keep the batch's linear ids, not its slot numbers:
+        # slots are resolved against the tags right before each kernel
+        linear = host._prefetch_cache(indices, offsets)
+        cache_loc = host._cache_locations(linear)
         out = torch.ops.trec_amd.tbe_forward_pooled(
             host.weights,
             host._table_elem_offsets,
@@ -94,7 +97,7 @@ class _TBEPooledFunction(torch.autograd.Function):
         )
         ctx.host = host
         ctx.save_for_backward(
-            indices, offsets, psw if psw is not None else host._empty_f, cache_loc
+            indices, offsets, psw if psw is not None else host._empty_f, linear
         )
         ctx.has_psw = psw is not None
         return out
@@ -102,10 +105,12 @@ class _TBEPooledFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad):  # type: ignore[override]
         host = ctx.host
-        indices, offsets, psw, cache_loc = ctx.saved_tensors
+        indices, offsets, psw, linear = ctx.saved_tensors
         psw_t = psw if ctx.has_psw else None
+        # a prefetch since the forward may have evicted or re-inserted rows
         grad_psw = host._backward_pooled(
-            grad.contiguous(), indices, offsets, psw_t, cache_loc=cache_loc
+            grad.contiguous(), indices, offsets, psw_t,
+            cache_loc=host._cache_locations(linear),
         )
         return None, None, None, None, grad_psw
 
@@ -117,6 +122,7 @@ class _TBEVbeFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dummy, host, indices, offsets, psw, bag_offsets, out_offsets, out_numel):  # type: ignore[override]
+        host._cache_bypass()
         out = torch.ops.trec_amd.tbe_forward_pooled_vbe(
             host.weights,
             host._table_elem_offsets,
@@ -146,6 +152,7 @@ class _TBEVbeFunction(torch.autograd.Function):
         indices, offsets, psw, bag_offsets, out_offsets = ctx.saved_tensors
         psw_t = psw if ctx.has_psw else None
         grad = grad.contiguous()
+        host._cache_write_back_and_invalidate()
         grad_psw = None
         if psw_t is not None and ctx.needs_input_grad[4]:
             # read rows BEFORE the fused update rewrites them
@@ -157,6 +164,7 @@ class _TBEVbeFunction(torch.autograd.Function):
 class _TBESeqFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, dummy, host, indices, feat_val_offsets):  # type: ignore[override]
+        host._cache_bypass()
         out = torch.ops.trec_amd.tbe_forward_seq(
             host.weights,
             host._table_elem_offsets,
@@ -567,6 +575,9 @@ class TableBatchedEmbeddingBags(nn.Module):
             pos_table = self._feat_table_t.to(torch.int64)[fpsw].to(torch.int32)
             if grad.dtype != torch.float32:
                 grad = grad.float()  # psw-grad kernel reads fp32 rows
+            # the psw-grad kernel reads the host table only: bring it up to
+            # date with the dirty cached rows (the cache stays valid)
+            self.flush_cache()
             grad_psw_out = torch.ops.trec_amd.tbe_grad_per_sample_weights(
                 self.weights if not isinstance(self.weights, nn.Parameter) else self.weights.data,
                 self._table_elem_offsets,
@@ -682,34 +693,104 @@ class TableBatchedEmbeddingBags(nn.Module):
             self._max_D,
         )
 
-    def prefetch(self, indices: torch.Tensor, offsets: torch.Tensor) -> None:
+    # -- lxu cache (MANAGED_CACHING) -----------------------------------------
+    #
+    # Coherence rule: a row's current value lives in its cache slot while its
+    # id is in ``cache_tags`` and in the pinned host table otherwise. Eviction
+    # and flush_cache() write the slot back; population copies the host row in.
+    #  * The pooled path reads and updates cached rows in place. A slot number
+    #    is only good until the next population, so prefetch() queues the
+    #    batch's linear ids and the forward and the backward each resolve
+    #    them against the tags right before their kernel (an evicted row
+    #    resolves to -1 = the host row the eviction has just brought up to
+    #    date).
+    #  * The VBE and sequence paths (forward and backward) and the
+    #    per-sample-weight gradient kernel address the host table only. The
+    #    first two write the cache back and invalidate it on entry
+    #    (flush_cache() + tags = -1); the psw-gradient kernel runs after a
+    #    flush_cache() and leaves the cache valid.
+
+    def prefetch(
+        self,
+        indices: torch.Tensor,
+        offsets: torch.Tensor,
+        batch_size_per_feature: Optional[List[int]] = None,
+    ) -> None:
         """Explicit cache prefetch (reference SplitTBE.prefetch()): populate
-        the lxu cache ahead of time; the next forward pops the locations.
-        Used by PrefetchTrainPipelineSparseDist's prefetch stream."""
+        the lxu cache ahead of time and queue the batch's linear ids; the
+        forwards consume the queue in order, one entry per forward.
+        Used by PrefetchTrainPipelineSparseDist's prefetch stream.
+
+        A variable-batch input (``batch_size_per_feature`` given) only queues
+        a marker: its forward bypasses the cache, and the fixed-batch bag
+        layout assumed here would mis-linearise its ids."""
         if not self._uvm_caching:
             return
-        loc = self._populate_and_lookup(indices, offsets)
-        self._prefetched.append(loc)
+        if batch_size_per_feature is not None:
+            self._prefetched.append((indices.numel(), None))
+            return
+        linear = self._linear_ids(indices, offsets)
+        self._populate(linear)
+        self._prefetched.append((indices.numel(), linear))
 
     def _prefetch_cache(
         self, indices: torch.Tensor, offsets: torch.Tensor
     ) -> torch.Tensor:
-        """Per-position cache slots for this batch: pop a prefetched batch if
-        the pipeline ran prefetch(), else populate inline.
+        """Linear ids of this batch, its rows populated: pop the batch's
+        prefetch() entry if there is one, else populate inline.
 
         Returns the empty tensor when caching is off (kernels then read the
         weights buffer directly)."""
         if not self._uvm_caching:
             return self._empty_i
         if self._prefetched:
-            return self._prefetched.popleft()
-        return self._populate_and_lookup(indices, offsets)
+            numel, linear = self._prefetched.popleft()
+            if numel != indices.numel():
+                raise RuntimeError(
+                    f"lxu cache: the oldest prefetch() was for {numel} indices, "
+                    f"this forward has {indices.numel()}; forwards must follow "
+                    "the order of their prefetch() calls"
+                )
+            if linear is not None:
+                # made on the prefetch stream, used (and freed) on this one
+                linear.record_stream(torch.cuda.current_stream())
+                return linear
+        linear = self._linear_ids(indices, offsets)
+        self._populate(linear)
+        return linear
 
-    def _populate_and_lookup(
-        self, indices: torch.Tensor, offsets: torch.Tensor
-    ) -> torch.Tensor:
+    def _cache_locations(self, linear: torch.Tensor) -> torch.Tensor:
+        """Per-position cache slot (-1: host row) as of now, on this stream."""
+        if not self._uvm_caching or linear.numel() == 0:
+            return self._empty_i
+        return torch.ops.trec_amd.lxu_cache_lookup(linear, self.cache_tags)
+
+    def _cache_write_back_and_invalidate(self) -> None:
+        """Make the host table current and empty the cache (entry of the
+        paths that address the host table only)."""
+        if not self._uvm_caching:
+            return
+        self.flush_cache()
+        self.cache_tags.fill_(-1)
+
+    def _cache_bypass(self) -> None:
+        """Entry of a VBE / sequence forward on a cached module: drop the
+        prefetch() entry queued for this batch, then write back + invalidate."""
+        if not self._uvm_caching:
+            return
+        if self._prefetched:
+            self._prefetched.popleft()
+        self._cache_write_back_and_invalidate()
+
+    def _linear_ids(self, indices: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
         B = (offsets.numel() - 1) // self._num_features
         _, _, linear, _ = self._bag_metadata(indices, offsets, B)
+        return linear
+
+    def _populate(self, linear: torch.Tensor) -> None:
+        if linear.numel() == 0:
+            return
+        ops.hip_ops()  # a prefetch() may be the module's first GPU call
         sorted_lin, _ = torch.ops.trec_amd.sort_pairs(linear, _bits_needed(self._total_rows))
         seg_offsets, num_runs = torch.ops.trec_amd.tbe_backward_prep(sorted_lin)
         uniq = torch.ops.trec_amd.gather_run_heads(sorted_lin, seg_offsets, num_runs)
@@ -739,12 +820,24 @@ class TableBatchedEmbeddingBags(nn.Module):
             self.cache_weights.shape[1],
             self._cache_timestamp,
         )
+
+    def _populate_and_lookup(
+        self, indices: torch.Tensor, offsets: torch.Tensor
+    ) -> torch.Tensor:
+        """Populate the batch's rows and return its per-position slots as of
+        the end of that population (-1: not resident, e.g. displaced by a
+        later id of the same batch)."""
+        linear = self._linear_ids(indices, offsets)
+        if linear.numel() == 0:
+            return torch.empty(0, dtype=torch.int32, device=linear.device)
+        self._populate(linear)
         return torch.ops.trec_amd.lxu_cache_lookup(linear, self.cache_tags)
 
     def flush_cache(self) -> None:
         """Write cached rows back to the host table (before reading weights)."""
         if not self._uvm_caching:
             return
+        ops.hip_ops()
         torch.ops.trec_amd.lxu_cache_flush(
             self.weights,
             self._table_row_offsets,
@@ -762,7 +855,11 @@ class TableBatchedEmbeddingBags(nn.Module):
         batch_size_per_feature: List[int],
         per_sample_weights: Optional[torch.Tensor] = None,
     ) -> torch.Tensor:
-        """Variable-batch pooled forward -> 1-D packed [sum_f B_f * D_f]."""
+        """Variable-batch pooled forward -> 1-D packed [sum_f B_f * D_f].
+
+        On an lxu-cached module this path addresses the host table only: its
+        forward and its backward first write the cache back and invalidate it
+        (the locations are not wired through the VBE kernels)."""
         assert self.optimizer != OPT_DENSE, (
             "VBE v1 requires a fused optimizer (rowwise_adagrad/sgd); the "
             "DENSE kernel's autograd grad surface is not wired for the "
@@ -788,6 +885,25 @@ class TableBatchedEmbeddingBags(nn.Module):
             self._dummy, self, indices, offsets, per_sample_weights,
             bag_offsets, out_offsets, out_off[-1],
         )
+
+    def _forward_seq(
+        self, indices: torch.Tensor, offsets: torch.Tensor, dedup: bool = False
+    ) -> torch.Tensor:
+        """Sequence (non-pooled) GPU forward -> [N, max_D]; a row of a
+        narrower table fills its first D columns only.
+
+        On an lxu-cached module this path addresses the host table only: its
+        forward and its backward first write the cache back and invalidate it."""
+        ops.hip_ops()
+        F = self._num_features
+        B = (offsets.numel() - 1) // F
+        # feature value-range offsets: offsets at bag boundaries f*B
+        feat_val_offsets = offsets[:: B][: F + 1].contiguous()
+        if feat_val_offsets.numel() < F + 1:
+            feat_val_offsets = torch.cat([feat_val_offsets, offsets[-1:]])
+        if dedup:
+            return _TBESeqDedupFunction.apply(self._dummy, self, indices, feat_val_offsets)
+        return _TBESeqFunction.apply(self._dummy, self, indices, feat_val_offsets)
 
     def _backward_vbe(
         self,
@@ -854,6 +970,7 @@ class TableBatchedEmbeddingBags(nn.Module):
         self, grad: torch.Tensor, indices: torch.Tensor, feat_val_offsets: torch.Tensor
     ) -> None:
         """Sequence backward: grad row == position; same fused segment kernel."""
+        self._cache_write_back_and_invalidate()
         N = indices.numel()
         counts = feat_val_offsets[1:] - feat_val_offsets[:-1]
         f = torch.repeat_interleave(
@@ -1086,6 +1203,8 @@ class TableBatchedEmbeddings(nn.Module):
         weights_precision: str = "fp32",
         use_index_dedup: bool = False,
         output_dtype: str = "fp32",
+        location: EmbeddingLocation = EmbeddingLocation.DEVICE,
+        cache_load_factor: float = 0.2,
     ) -> None:
         super().__init__()
         self._use_index_dedup = use_index_dedup
@@ -1103,6 +1222,8 @@ class TableBatchedEmbeddings(nn.Module):
             init_max=init_max,
             weights_precision=weights_precision,
             output_dtype=output_dtype,
+            location=location,
+            cache_load_factor=cache_load_factor,
         )
         self._dim = next(iter(dims)) if dims else 0
 
@@ -1139,15 +1260,7 @@ class TableBatchedEmbeddings(nn.Module):
         B = (offsets.numel() - 1) // host._num_features
         if not indices.is_cuda:
             return _TBESeqCpuFunction.apply(host._dummy, host, indices, offsets, B)
-        ops.hip_ops()
-        # feature value-range offsets: offsets at bag boundaries f*B
-        F = host._num_features
-        feat_val_offsets = offsets[:: B][: F + 1].contiguous()
-        if feat_val_offsets.numel() < F + 1:
-            feat_val_offsets = torch.cat([feat_val_offsets, offsets[-1:]])
-        if self._use_index_dedup:
-            return _TBESeqDedupFunction.apply(host._dummy, host, indices, feat_val_offsets)
-        return _TBESeqFunction.apply(host._dummy, host, indices, feat_val_offsets)
+        return host._forward_seq(indices, offsets, self._use_index_dedup)
 
 
 class _TBESeqDedupFunction(torch.autograd.Function):
@@ -1162,6 +1275,7 @@ class _TBESeqDedupFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dummy, host, indices, feat_val_offsets):  # type: ignore[override]
+        host._cache_bypass()
         N = indices.numel()
         counts = feat_val_offsets[1:] - feat_val_offsets[:-1]
         f = torch.repeat_interleave(
