@@ -406,8 +406,9 @@ def _pair_tables(F1: int, device: torch.device):
     if key not in _PAIR_TABLES:
         tri = torch.triu_indices(F1, F1, offset=1)
         P = tri.shape[1]
-        pi = tri[0].to(torch.int8)
-        pj = tri[1].to(torch.int8)
+        # int16: the VALU kernel takes any F, and int8 wraps above row 127
+        pi = tri[0].to(torch.int16)
+        pj = tri[1].to(torch.int16)
         pair_col = torch.full((F1 * F1,), -1, dtype=torch.int32)
         for p in range(P):
             i, j = int(tri[0, p]), int(tri[1, p])

@@ -16,6 +16,8 @@ constexpr int kNumXCD = 8;
 constexpr int kNumCU = 256;
 // memory-bound launch cap (Guideline 11): ~8 blocks/CU
 constexpr int kMaxBlocks = kNumCU * 8;
+// LDS per CU, which is also the most one workgroup can ask for
+constexpr int kLdsBytesPerCU = 160 * 1024;
 
 #define TREC_HIP_CHECK(cmd)                                                   \
   do {                                                                        \

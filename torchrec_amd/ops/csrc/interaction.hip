@@ -30,8 +30,8 @@ static inline hipStream_t ia_stream() {
 __global__ void __launch_bounds__(kBlockThreads) interaction_fwd_kernel(
     const float* __restrict__ dense,   // [B, D]
     const float* __restrict__ sparse,  // [B, F, D]
-    const int8_t* __restrict__ pi,     // [P] row i of pair p
-    const int8_t* __restrict__ pj,     // [P] row j of pair p
+    const int16_t* __restrict__ pi,    // [P] row i of pair p
+    const int16_t* __restrict__ pj,    // [P] row j of pair p
     int B, int F1, int D, int P, float* __restrict__ out /* [B, D+P] */) {
   // 256 threads (4 waves) per sample: staging and the P pair-dots spread
   // across the whole block (351 pairs -> ~1.4 per lane instead of 5.5 on a
@@ -150,15 +150,20 @@ at::Tensor interaction_forward(const at::Tensor& dense, const at::Tensor& sparse
   int D = dense.size(1);
   int F1 = sparse.size(1) + 1;
   int P = pi.numel();
+  TORCH_CHECK(P == F1 * (F1 - 1) / 2, "interaction: pair table does not match F");
   auto out = at::empty({B, D + P}, dense.options());
   if (B == 0) return out;
   TORCH_CHECK(D % 4 == 0, "interaction kernel needs D %% 4 == 0");
-  int lds_bytes = F1 * (D / 4 + 1) * sizeof(float4);
+  int64_t lds_need = static_cast<int64_t>(F1) * (D / 4 + 1) * sizeof(float4);
+  TORCH_CHECK(lds_need <= kLdsBytesPerCU, "interaction: the [F+1, D] tile needs ", lds_need,
+              " B of LDS, a workgroup has ", kLdsBytesPerCU);
+  int lds_bytes = static_cast<int>(lds_need);
   int grid = std::min<int>(B, kNumCU * 32);
   hipLaunchKernelGGL(interaction_fwd_kernel, dim3(grid), dim3(kBlockThreads), lds_bytes, ia_stream(),
                      dense.contiguous().data_ptr<float>(),
-                     sparse.contiguous().data_ptr<float>(), pi.data_ptr<int8_t>(),
-                     pj.data_ptr<int8_t>(), B, F1, D, P, out.data_ptr<float>());
+                     sparse.contiguous().data_ptr<float>(), pi.data_ptr<int16_t>(),
+                     pj.data_ptr<int16_t>(), B, F1, D, P, out.data_ptr<float>());
+  TREC_HIP_CHECK(hipGetLastError());
   return out;
 }
 
@@ -169,12 +174,18 @@ std::tuple<at::Tensor, at::Tensor> interaction_backward(
   int D = dense.size(1);
   int F1 = sparse.size(1) + 1;
   int P = grad_out.size(1) - D;
-  auto d_dense = at::empty_like(dense);
-  auto d_sparse = at::empty_like(sparse);
+  // the kernel writes contiguous [B, D] / [B, F, D]; empty_like would keep
+  // the strides of a transposed input
+  auto d_dense = at::empty(dense.sizes(), dense.options());
+  auto d_sparse = at::empty(sparse.sizes(), sparse.options());
   if (B == 0) return {d_dense, d_sparse};
   TORCH_CHECK(D % 4 == 0, "interaction kernel needs D %% 4 == 0");
-  int lds_bytes = F1 * (D / 4 + 1) * sizeof(float4) + P * sizeof(float)
-                  + F1 * F1 * sizeof(int32_t);
+  int64_t lds_need = static_cast<int64_t>(F1) * (D / 4 + 1) * sizeof(float4)
+                     + static_cast<int64_t>(P) * sizeof(float)
+                     + static_cast<int64_t>(F1) * F1 * sizeof(int32_t);
+  TORCH_CHECK(lds_need <= kLdsBytesPerCU, "interaction backward: tile, pair gradients and ",
+              "pair map need ", lds_need, " B of LDS, a workgroup has ", kLdsBytesPerCU);
+  int lds_bytes = static_cast<int>(lds_need);
   int grid = std::min<int>(B, kMaxBlocks);
   hipLaunchKernelGGL(interaction_bwd_kernel, dim3(grid), dim3(kBlockThreads), lds_bytes,
                      ia_stream(), grad_out.contiguous().data_ptr<float>(),
@@ -182,6 +193,7 @@ std::tuple<at::Tensor, at::Tensor> interaction_backward(
                      sparse.contiguous().data_ptr<float>(),
                      pair_col_plus_d.data_ptr<int32_t>(), B, F1, D, P,
                      d_dense.data_ptr<float>(), d_sparse.data_ptr<float>());
+  TREC_HIP_CHECK(hipGetLastError());
   return {d_dense, d_sparse};
 }
 

@@ -56,7 +56,7 @@ template <typename io_t>
 __global__ void __launch_bounds__(kIWaves * kWaveSize) interaction_mfma_fwd_kernel(
     const io_t* __restrict__ dense,   // [B, D]
     const io_t* __restrict__ sparse,  // [B, F1-1, D]
-    const int8_t* __restrict__ pi, const int8_t* __restrict__ pj,  // [P]
+    const int16_t* __restrict__ pi, const int16_t* __restrict__ pj,  // [P]
     int B, int F1, int D, int P, io_t* __restrict__ out /* [B, D+P] */) {
   extern __shared__ char lds[];
   const int l = threadIdx.x & 63;
@@ -236,6 +236,7 @@ at::Tensor interaction_mfma_forward(const at::Tensor& dense, const at::Tensor& s
   int P = pi.numel();
   TORCH_CHECK(D % 32 == 0 && D <= 256, "interaction_mfma needs D % 32 == 0, D <= 256");
   TORCH_CHECK(F1 <= 32, "interaction_mfma needs <= 31 sparse features");
+  TORCH_CHECK(P == F1 * (F1 - 1) / 2, "interaction_mfma: pair table does not match F");
   auto out = at::empty({B, D + P}, dense.options());
   if (B == 0) return out;
   int lds_bytes = kIWaves * (32 * D * 2 + 32 * 32 * 4);
@@ -251,8 +252,9 @@ at::Tensor interaction_mfma_forward(const at::Tensor& dense, const at::Tensor& s
                          dim3(kIWaves * kWaveSize), lds_bytes, stream,
                          reinterpret_cast<const dev_t*>(dense.contiguous().data_ptr<scalar_t>()),
                          reinterpret_cast<const dev_t*>(sparse.contiguous().data_ptr<scalar_t>()),
-                         pi.data_ptr<int8_t>(), pj.data_ptr<int8_t>(), B, F1, D, P,
+                         pi.data_ptr<int16_t>(), pj.data_ptr<int16_t>(), B, F1, D, P,
                          reinterpret_cast<dev_t*>(out.data_ptr<scalar_t>()));
+      TREC_HIP_CHECK(hipGetLastError());
     }
   });
   return out;
@@ -267,8 +269,10 @@ std::tuple<at::Tensor, at::Tensor> interaction_mfma_backward(
   int P = grad_out.size(1) - D;
   TORCH_CHECK(D % 32 == 0 && D <= 256 && F1 <= 32);
   TORCH_CHECK(grad_out.scalar_type() == dense.scalar_type());
-  auto d_dense = at::empty_like(dense);
-  auto d_sparse = at::empty_like(sparse);
+  // the kernel writes contiguous [B, D] / [B, F, D]; empty_like would keep
+  // the strides of a transposed input
+  auto d_dense = at::empty(dense.sizes(), dense.options());
+  auto d_sparse = at::empty(sparse.sizes(), sparse.options());
   if (B == 0) return {d_dense, d_sparse};
   constexpr int kStrideE = 40;
   int lds_bytes = 32 * 32 * 4 + 32 * kStrideE * 2 + D * kStrideE * 2;
@@ -288,6 +292,7 @@ std::tuple<at::Tensor, at::Tensor> interaction_mfma_backward(
                          pair_col.data_ptr<int32_t>(), B, F1, D, P,
                          reinterpret_cast<dev_t*>(d_dense.data_ptr<scalar_t>()),
                          reinterpret_cast<dev_t*>(d_sparse.data_ptr<scalar_t>()));
+      TREC_HIP_CHECK(hipGetLastError());
     }
   });
   return {d_dense, d_sparse};

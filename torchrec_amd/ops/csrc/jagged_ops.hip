@@ -405,7 +405,9 @@ at::Tensor permute_pooled_embs(const at::Tensor& values, const at::Tensor& in_of
   int B = values.size(0);
   int64_t D_total = values.size(1);
   int G = order.numel();
-  auto out = at::empty_like(values);
+  // written as contiguous [B, sum_D]; empty_like would keep a transposed
+  // input's strides
+  auto out = at::empty(values.sizes(), values.options());
   if (values.numel() == 0) return out;
   auto v = values.contiguous();
   auto io = in_offsets.to(at::kLong).to(values.device()).contiguous();
