@@ -137,9 +137,11 @@ def bench_col_sum(M=8192, N=1024):
     }))
 
 
-def bench_quant_tbe(B=8192, D=128, tables=26, rows=100_000, weight_dtype=None, repeats=1):
+def bench_quant_tbe(B=8192, D=128, tables=26, rows=100_000, weight_dtype=None, repeats=1,
+                    output_dtype=torch.float32, emit=True):
     """Quantized inference TBE forward at ``weight_dtype`` (default INT8) vs
-    the fp32 training TBE forward. Returns the ``repeats`` timings in us."""
+    the fp32 training TBE forward, writing ``output_dtype``. Returns the
+    ``repeats`` timings in us; ``emit=False`` leaves the printing to the caller."""
     from torchrec_amd.modules.embedding_configs import DATA_TYPE_NUM_BITS, DataType
     from torchrec_amd.quant.embedding_modules import (
         QuantTableBatchedEmbeddingBags,
@@ -152,7 +154,8 @@ def bench_quant_tbe(B=8192, D=128, tables=26, rows=100_000, weight_dtype=None, r
     torch.manual_seed(0)
     specs = [(f"t{i}", rows, D) for i in range(tables)]
     q = QuantTableBatchedEmbeddingBags(
-        specs, device=torch.device("cuda"), weight_dtypes=[weight_dtype] * tables
+        specs, device=torch.device("cuda"), weight_dtypes=[weight_dtype] * tables,
+        output_dtype=output_dtype,
     )
     for i in range(tables):
         q.load_float_table(i, torch.randn(rows, D, device="cuda"))
@@ -163,6 +166,8 @@ def bench_quant_tbe(B=8192, D=128, tables=26, rows=100_000, weight_dtype=None, r
     times = [
         _time_kernel(lambda: q(indices, offsets), iters=5000, warmup=20) for _ in range(repeats)
     ]
+    if not emit:
+        return times
     qt = sorted(times)[len(times) // 2]
     res = {
         "bench": "quant_tbe_fwd", "weight_dtype": weight_dtype.name, "B": B,
@@ -173,6 +178,8 @@ def bench_quant_tbe(B=8192, D=128, tables=26, rows=100_000, weight_dtype=None, r
     if repeats > 1:
         res[f"{name}_us_runs"] = [round(t, 1) for t in times]
         res[f"{name}_spread_us"] = round(max(times) - min(times), 1)
+    if output_dtype != torch.float32:
+        res["output_dtype"] = str(output_dtype).replace("torch.", "")
     if weight_dtype == DataType.INT8:
         f32 = TableBatchedEmbeddingBags(specs, device=torch.device("cuda"))
         res["fp32_us"] = round(_time_kernel(lambda: f32(indices, offsets)), 1)
@@ -198,11 +205,38 @@ def bench_quant_suite():
         }))
 
 
+def bench_quant_out_suite(B=8192, D=128, tables=26):
+    """Per width: fp32 output five times (median + max-min spread = the noise
+    margin of this run), then bf16 and fp16 output three times each, all in
+    this process. One line per (width, output dtype)."""
+    from torchrec_amd.modules.embedding_configs import DataType
+
+    def line(dt, out, times, **extra):
+        print(json.dumps({
+            "bench": "quant_tbe_fwd_out", "weight_dtype": dt.name,
+            "output_dtype": str(out).replace("torch.", ""), "B": B, "tables": tables, "D": D,
+            "out_bytes": B * tables * D * torch.empty(0, dtype=out).element_size(),
+            "us": round(sorted(times)[len(times) // 2], 1),
+            "us_runs": [round(t, 1) for t in times], **extra,
+        }))
+
+    for dt in (DataType.INT8, DataType.INT4, DataType.INT2):
+        f32 = bench_quant_tbe(B, D, tables, weight_dtype=dt, repeats=5, emit=False)
+        med, spread = sorted(f32)[2], max(f32) - min(f32)
+        line(dt, torch.float32, f32, spread_us=round(spread, 1))
+        for out in (torch.bfloat16, torch.float16):
+            t = bench_quant_tbe(
+                B, D, tables, weight_dtype=dt, repeats=3, output_dtype=out, emit=False
+            )
+            line(dt, out, t, fp32_median_us=round(med, 1), fp32_spread_us=round(spread, 1),
+                 within_noise_or_faster=bool(sorted(t)[1] <= med + spread))
+
+
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--suite", default="all",
                    choices=["all", "tbe", "tbe_sweep", "interaction", "sort",
-                            "col_sum", "quant"])
+                            "col_sum", "quant", "quant_out"])
     a = p.parse_args()
     assert torch.cuda.is_available(), "run on a GPU box"
     if a.suite in ("all", "tbe"):
@@ -224,3 +258,5 @@ if __name__ == "__main__":
         bench_col_sum()
     if a.suite in ("all", "quant"):
         bench_quant_suite()
+    if a.suite == "quant_out":
+        bench_quant_out_suite()

@@ -130,6 +130,7 @@ class GroupedPooledEmbeddingsLookup(nn.Module):
                     pooling=pool,
                     device=device,
                     weight_dtypes=[quant_data_type(t.data_type) for t in group],
+                    output_dtype=self._out_torch_dtype,
                 )
                 self._emb_modules.append(qtbe)
                 self._feature_splits.append(

@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from torchrec_amd.distributed.embedding import ShardedEmbeddingCollection
 from torchrec_amd.distributed.embedding_sharding import ShardedTableLocal
+from torchrec_amd.distributed.quant_embeddingbag import with_module_output_dtype
 from torchrec_amd.distributed.types import (
     EmbeddingModuleShardingPlan,
     ModuleSharder,
@@ -51,11 +52,12 @@ class _QuantSeqLookup(nn.Module):
             w = qtbe.dequantized_table(t)
             lo, hi = int(offsets[f * B]), int(offsets[(f + 1) * B])
             outs.append(w[indices[lo:hi]])
-        return (
+        rows = (
             torch.cat(outs, dim=0)
             if outs
             else torch.zeros(0, self._dim, device=indices.device)
         )
+        return qtbe.to_output_dtype(rows)
 
 
 class ShardedQuantEmbeddingCollection(ShardedEmbeddingCollection):
@@ -70,6 +72,14 @@ class ShardedQuantEmbeddingCollection(ShardedEmbeddingCollection):
         device: Optional[torch.device] = None,
     ) -> None:
         object.__setattr__(self, "_quant_device_pre", device)
+        fused_params = with_module_output_dtype(fused_params, module)
+        object.__setattr__(
+            self,
+            "_quant_out_dtype_pre",
+            {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[
+                fused_params["output_dtype"]
+            ],
+        )
         super().__init__(
             module, table_name_to_parameter_sharding, env, fused_params, device
         )
@@ -101,6 +111,7 @@ class ShardedQuantEmbeddingCollection(ShardedEmbeddingCollection):
             feature_table_map=[i for i, t in enumerate(tables) for _ in t.feature_names],
             device=self._quant_device_pre,
             weight_dtypes=[quant_data_type(t.data_type) for t in tables],
+            output_dtype=self._quant_out_dtype_pre,
         )
         return _QuantSeqLookup(qtbe, D)
 

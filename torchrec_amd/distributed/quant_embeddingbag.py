@@ -29,6 +29,20 @@ from torchrec_amd.quant.embedding_modules import (
 )
 
 
+_OUT_DTYPE_NAME = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.float16: "fp16"}
+
+
+def with_module_output_dtype(
+    fused_params: Optional[Dict[str, Any]], module: Any
+) -> Dict[str, Any]:
+    """``fused_params`` with the unsharded quant module's ``output_dtype`` where
+    the caller named none: sharding a bf16 module gives a bf16 sharded module."""
+    fused_params = dict(fused_params or {})
+    if "output_dtype" not in fused_params:
+        fused_params["output_dtype"] = _OUT_DTYPE_NAME[module.output_dtype()]
+    return fused_params
+
+
 class ShardedQuantEmbeddingBagCollection(ShardedEmbeddingBagCollection):
     """Shards a quantized EBC; packed rows (any width: the slice is by whole
     rows at the table's own stride) are sliced per shard."""
@@ -41,6 +55,7 @@ class ShardedQuantEmbeddingBagCollection(ShardedEmbeddingBagCollection):
         fused_params: Optional[Dict[str, Any]] = None,
         device: Optional[torch.device] = None,
     ) -> None:
+        fused_params = with_module_output_dtype(fused_params, module)
         super().__init__(module, table_name_to_parameter_sharding, env, fused_params, device)
         # load packed rows into the quant lookups (TW: whole table; RW: row slice)
         src = module._tbe

@@ -116,12 +116,13 @@ at::Tensor tbe_forward_pooled_int8(const at::Tensor& qweights,
                                    const at::Tensor& feat_table, const at::Tensor& d_out_offsets,
                                    const at::Tensor& indices, const at::Tensor& offsets,
                                    const at::Tensor& per_sample_weights, int64_t B,
-                                   int64_t total_D, int64_t max_D, bool mean_pool);
+                                   int64_t total_D, int64_t max_D, bool mean_pool,
+                                   int64_t output_dtype);
 at::Tensor tbe_forward_seq_int8(const at::Tensor& qweights,
                                 const at::Tensor& table_byte_offsets, const at::Tensor& dims,
                                 const at::Tensor& feat_table,
                                 const at::Tensor& feat_val_offsets, const at::Tensor& indices,
-                                int64_t D_out, int64_t max_D);
+                                int64_t D_out, int64_t max_D, int64_t output_dtype);
 at::Tensor quantize_rowwise_nbit(const at::Tensor& weights, int64_t bits);
 at::Tensor tbe_forward_pooled_nbit(const at::Tensor& qweights,
                                    const at::Tensor& table_byte_offsets, const at::Tensor& dims,
@@ -129,12 +130,13 @@ at::Tensor tbe_forward_pooled_nbit(const at::Tensor& qweights,
                                    const at::Tensor& d_out_offsets, const at::Tensor& indices,
                                    const at::Tensor& offsets,
                                    const at::Tensor& per_sample_weights, int64_t B,
-                                   int64_t total_D, int64_t max_units, bool mean_pool);
+                                   int64_t total_D, int64_t max_units, bool mean_pool,
+                                   int64_t output_dtype);
 at::Tensor tbe_forward_seq_nbit(const at::Tensor& qweights,
                                 const at::Tensor& table_byte_offsets, const at::Tensor& dims,
                                 const at::Tensor& weight_bits, const at::Tensor& feat_table,
                                 const at::Tensor& feat_val_offsets, const at::Tensor& indices,
-                                int64_t D_out, int64_t max_units);
+                                int64_t D_out, int64_t max_units, int64_t output_dtype);
 
 // interaction.hip
 at::Tensor col_sum(const at::Tensor& input);
@@ -261,21 +263,22 @@ TORCH_LIBRARY(trec_amd, m) {
   m.def(
       "tbe_forward_pooled_int8(Tensor qweights, Tensor table_byte_offsets, Tensor dims,"
       " Tensor feat_table, Tensor d_out_offsets, Tensor indices, Tensor offsets,"
-      " Tensor per_sample_weights, int B, int total_D, int max_D, bool mean_pool) -> Tensor");
+      " Tensor per_sample_weights, int B, int total_D, int max_D, bool mean_pool,"
+      " int output_dtype=0) -> Tensor");
   m.def(
       "tbe_forward_seq_int8(Tensor qweights, Tensor table_byte_offsets, Tensor dims,"
-      " Tensor feat_table, Tensor feat_val_offsets, Tensor indices, int D_out, int max_D)"
-      " -> Tensor");
+      " Tensor feat_table, Tensor feat_val_offsets, Tensor indices, int D_out, int max_D,"
+      " int output_dtype=0) -> Tensor");
   m.def("quantize_rowwise_nbit(Tensor weights, int bits) -> Tensor");
   m.def(
       "tbe_forward_pooled_nbit(Tensor qweights, Tensor table_byte_offsets, Tensor dims,"
       " Tensor weight_bits, Tensor feat_table, Tensor d_out_offsets, Tensor indices,"
       " Tensor offsets, Tensor per_sample_weights, int B, int total_D, int max_units,"
-      " bool mean_pool) -> Tensor");
+      " bool mean_pool, int output_dtype=0) -> Tensor");
   m.def(
       "tbe_forward_seq_nbit(Tensor qweights, Tensor table_byte_offsets, Tensor dims,"
       " Tensor weight_bits, Tensor feat_table, Tensor feat_val_offsets, Tensor indices,"
-      " int D_out, int max_units) -> Tensor");
+      " int D_out, int max_units, int output_dtype=0) -> Tensor");
   m.def("col_sum(Tensor input) -> Tensor");
   m.def("interaction_forward(Tensor dense, Tensor sparse, Tensor pi, Tensor pj) -> Tensor");
   m.def("relu_bwd_col_sum(Tensor grad_out, Tensor y) -> (Tensor, Tensor)");

@@ -93,9 +93,22 @@ at::Tensor quantize_rowwise_int8(const at::Tensor& weights) {
 
 // ---------------------------------------------------------------------------
 // pooled int8 forward: same slot scheme as the fp32 TBE
+//
+// out_t (float / __hip_bfloat16 / __half) is the output element type of all
+// four forward kernels below. Dequant, per-sample weight, the pool and the
+// MEAN scale stay in fp32 registers; the value is rounded once (to nearest
+// even, float2emb) in Vec4<out_t>::store. A 2-byte quad is an 8-byte store:
+// an output segment starts at a multiple of 4 elements, which is all it needs.
 // ---------------------------------------------------------------------------
 
-template <int LPS, int CHUNKS>
+// op-level output_dtype code (the training TBE's): 0 fp32, 1 bf16, 2 fp16
+static at::ScalarType quant_out_scalar_type(int64_t output_dtype, const char* op) {
+  TORCH_CHECK(output_dtype >= 0 && output_dtype <= 2, op,
+              ": output_dtype must be 0 (fp32), 1 (bf16) or 2 (fp16), got ", output_dtype);
+  return output_dtype == 1 ? at::kBFloat16 : (output_dtype == 2 ? at::kHalf : at::kFloat);
+}
+
+template <typename out_t, int LPS, int CHUNKS>
 __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_pooled_int8_kernel(
     const uint8_t* __restrict__ qweights,
     const int64_t* __restrict__ table_byte_offsets,  // [T]
@@ -105,7 +118,7 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_pooled_int8_kernel(
     const int64_t* __restrict__ indices,
     const int64_t* __restrict__ offsets,  // [F*B+1]
     const float* __restrict__ psw, int F, int B, int64_t total_D, bool mean_pool,
-    float* __restrict__ out) {
+    out_t* __restrict__ out) {
   int sl = threadIdx.x % LPS;
   int64_t slot = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / LPS;
   int64_t n_slots = (static_cast<int64_t>(gridDim.x) * blockDim.x) / LPS;
@@ -141,13 +154,13 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_pooled_int8_kernel(
     }
     float s = 1.f;
     if (mean_pool && i1 > i0) s = 1.f / static_cast<float>(i1 - i0);
-    float4* orow =
-        reinterpret_cast<float4*>(out + static_cast<int64_t>(b) * total_D + d_out_offsets[f]);
+    out_t* orow = out + static_cast<int64_t>(b) * total_D + d_out_offsets[f];
 #pragma unroll
     for (int c = 0; c < CHUNKS; ++c) {
       int col4 = c * LPS + sl;
       if (col4 * 4 < D)
-        orow[col4] = make_float4(acc[c].x * s, acc[c].y * s, acc[c].z * s, acc[c].w * s);
+        Vec4<out_t>::store(
+            orow, col4, make_float4(acc[c].x * s, acc[c].y * s, acc[c].z * s, acc[c].w * s));
     }
   }
 }
@@ -156,11 +169,12 @@ at::Tensor tbe_forward_pooled_int8(
     const at::Tensor& qweights, const at::Tensor& table_byte_offsets, const at::Tensor& dims,
     const at::Tensor& feat_table, const at::Tensor& d_out_offsets, const at::Tensor& indices,
     const at::Tensor& offsets, const at::Tensor& per_sample_weights, int64_t B,
-    int64_t total_D, int64_t max_D, bool mean_pool) {
+    int64_t total_D, int64_t max_D, bool mean_pool, int64_t output_dtype) {
   TORCH_CHECK((qweights.is_cuda() || qweights.is_pinned()) && qweights.scalar_type() == at::kByte);
   TORCH_CHECK(max_D % 4 == 0 && max_D <= 2048);
+  auto out_st = quant_out_scalar_type(output_dtype, "tbe_forward_pooled_int8");
   int F = feat_table.numel();
-  auto out = at::empty({B, total_D}, indices.options().dtype(at::kFloat));
+  auto out = at::empty({B, total_D}, indices.options().dtype(out_st));
   if (B == 0 || F == 0) return out;
   const float* psw_ptr =
       per_sample_weights.numel() > 0 ? per_sample_weights.data_ptr<float>() : nullptr;
@@ -168,13 +182,19 @@ at::Tensor tbe_forward_pooled_int8(
   int lps = (max_D <= 64) ? 16 : (max_D <= 128 ? 32 : 64);
   int chunks = (int)((max_D + lps * 4 - 1) / (lps * 4));
   int grid = grid_for(static_cast<int64_t>(F) * B * lps, kBlockThreads);
-#define TBE_Q_LAUNCH(LPS, CHUNKS)                                                         \
-  hipLaunchKernelGGL((tbe_fwd_pooled_int8_kernel<LPS, CHUNKS>), dim3(grid),               \
+#define TBE_Q_LAUNCH_T(out_t, LPS, CHUNKS)                                                \
+  hipLaunchKernelGGL((tbe_fwd_pooled_int8_kernel<out_t, LPS, CHUNKS>), dim3(grid),        \
                      dim3(kBlockThreads), 0, stream, uvm_ptr<uint8_t>(qweights),           \
                      table_byte_offsets.data_ptr<int64_t>(), dims.data_ptr<int32_t>(),    \
                      feat_table.data_ptr<int32_t>(), d_out_offsets.data_ptr<int64_t>(),   \
                      indices.data_ptr<int64_t>(), offsets.data_ptr<int64_t>(), psw_ptr,   \
-                     F, (int)B, total_D, mean_pool, out.data_ptr<float>())
+                     F, (int)B, total_D, mean_pool, static_cast<out_t*>(out.data_ptr()))
+#define TBE_Q_LAUNCH(LPS, CHUNKS)                                  \
+  do {                                                             \
+    if (output_dtype == 1) TBE_Q_LAUNCH_T(__hip_bfloat16, LPS, CHUNKS); \
+    else if (output_dtype == 2) TBE_Q_LAUNCH_T(__half, LPS, CHUNKS);    \
+    else TBE_Q_LAUNCH_T(float, LPS, CHUNKS);                       \
+  } while (0)
   if (lps == 16) TBE_Q_LAUNCH(16, 1);
   else if (lps == 32) TBE_Q_LAUNCH(32, 1);
   else switch (chunks) {
@@ -184,16 +204,17 @@ at::Tensor tbe_forward_pooled_int8(
     default: TBE_Q_LAUNCH(64, 8); break;
   }
 #undef TBE_Q_LAUNCH
+#undef TBE_Q_LAUNCH_T
   return out;
 }
 
 // sequence int8 forward: out[n] = dequant(row(idx[n]))
-template <int LPS, int CHUNKS>
+template <typename out_t, int LPS, int CHUNKS>
 __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_seq_int8_kernel(
     const uint8_t* __restrict__ qweights, const int64_t* __restrict__ table_byte_offsets,
     const int32_t* __restrict__ dims, const int32_t* __restrict__ feat_table,
     const int64_t* __restrict__ feat_val_offsets, const int64_t* __restrict__ indices, int F,
-    int64_t N, int64_t D_out, float* __restrict__ out) {
+    int64_t N, int64_t D_out, out_t* __restrict__ out) {
   int sl = threadIdx.x % LPS;
   int64_t slot = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / LPS;
   int64_t n_slots = (static_cast<int64_t>(gridDim.x) * blockDim.x) / LPS;
@@ -206,15 +227,15 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_seq_int8_kernel(
     const __half* sb = reinterpret_cast<const __half*>(row + D);
     float scale = __half2float(sb[0]);
     float bias = __half2float(sb[1]);
-    float4* orow = reinterpret_cast<float4*>(out + n * D_out);
+    out_t* orow = out + n * D_out;
 #pragma unroll
     for (int c = 0; c < CHUNKS; ++c) {
       int col4 = c * LPS + sl;
       if (col4 * 4 < D) {
         uchar4 q = reinterpret_cast<const uchar4*>(row)[col4];
-        orow[col4] =
-            make_float4(q.x * scale + bias, q.y * scale + bias, q.z * scale + bias,
-                        q.w * scale + bias);
+        Vec4<out_t>::store(orow, col4,
+                           make_float4(q.x * scale + bias, q.y * scale + bias,
+                                       q.z * scale + bias, q.w * scale + bias));
       }
     }
   }
@@ -223,22 +244,30 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_seq_int8_kernel(
 at::Tensor tbe_forward_seq_int8(
     const at::Tensor& qweights, const at::Tensor& table_byte_offsets, const at::Tensor& dims,
     const at::Tensor& feat_table, const at::Tensor& feat_val_offsets, const at::Tensor& indices,
-    int64_t D_out, int64_t max_D) {
+    int64_t D_out, int64_t max_D, int64_t output_dtype) {
   TORCH_CHECK((qweights.is_cuda() || qweights.is_pinned()) && max_D % 4 == 0 && max_D <= 2048);
+  auto out_st = quant_out_scalar_type(output_dtype, "tbe_forward_seq_int8");
   int64_t N = indices.numel();
-  auto out = at::empty({N, D_out}, indices.options().dtype(at::kFloat));
+  auto out = at::empty({N, D_out}, indices.options().dtype(out_st));
   if (N == 0) return out;
   int F = feat_table.numel();
   auto stream = q_stream();
   int lps = (max_D <= 64) ? 16 : (max_D <= 128 ? 32 : 64);
   int chunks = (int)((max_D + lps * 4 - 1) / (lps * 4));
   int grid = grid_for(N * lps, kBlockThreads);
-#define TBE_QS_LAUNCH(LPS, CHUNKS)                                                        \
-  hipLaunchKernelGGL((tbe_fwd_seq_int8_kernel<LPS, CHUNKS>), dim3(grid),                  \
+#define TBE_QS_LAUNCH_T(out_t, LPS, CHUNKS)                                               \
+  hipLaunchKernelGGL((tbe_fwd_seq_int8_kernel<out_t, LPS, CHUNKS>), dim3(grid),           \
                      dim3(kBlockThreads), 0, stream, uvm_ptr<uint8_t>(qweights),           \
                      table_byte_offsets.data_ptr<int64_t>(), dims.data_ptr<int32_t>(),    \
                      feat_table.data_ptr<int32_t>(), feat_val_offsets.data_ptr<int64_t>(),\
-                     indices.data_ptr<int64_t>(), F, N, D_out, out.data_ptr<float>())
+                     indices.data_ptr<int64_t>(), F, N, D_out,                            \
+                     static_cast<out_t*>(out.data_ptr()))
+#define TBE_QS_LAUNCH(LPS, CHUNKS)                                  \
+  do {                                                              \
+    if (output_dtype == 1) TBE_QS_LAUNCH_T(__hip_bfloat16, LPS, CHUNKS); \
+    else if (output_dtype == 2) TBE_QS_LAUNCH_T(__half, LPS, CHUNKS);    \
+    else TBE_QS_LAUNCH_T(float, LPS, CHUNKS);                       \
+  } while (0)
   if (lps == 16) TBE_QS_LAUNCH(16, 1);
   else if (lps == 32) TBE_QS_LAUNCH(32, 1);
   else switch (chunks) {
@@ -248,6 +277,7 @@ at::Tensor tbe_forward_seq_int8(
     default: TBE_QS_LAUNCH(64, 8); break;
   }
 #undef TBE_QS_LAUNCH
+#undef TBE_QS_LAUNCH_T
   return out;
 }
 
@@ -348,6 +378,9 @@ at::Tensor quantize_rowwise_nbit(const at::Tensor& weights, int64_t bits) {
 // (8 columns). A lane that owned a whole INT2 word would store four float4 at
 // a 64 B lane stride; that form measured 39 us against INT8's 33.5 us at the
 // bench shape, so no lane owns more than 8 columns (32 B, two float4).
+// With a 2-byte out_t the 8 columns are 16 B, but a segment start is only a
+// multiple of 4 elements (a D=20 table in front puts it at byte 40), so they
+// go out as two 8-byte quads like the fp32 pair, never as one 16-byte store.
 template <int BITS>
 struct CodeUnit {
   static constexpr int kCols = BITS == 8 ? 4 : 8;  // output columns per lane
@@ -360,11 +393,11 @@ struct CodeUnit {
 
 // One lane's share of a bag. BITS is a template parameter so the accumulators
 // stay in registers; the caller switches on the bag's table.
-template <int BITS, int LPS, int CHUNKS>
+template <typename out_t, int BITS, int LPS, int CHUNKS>
 __device__ __forceinline__ void pool_bag_nbit(
     const uint8_t* __restrict__ tab, int D, const int64_t* __restrict__ indices,
     const float* __restrict__ psw, int64_t i0, int64_t i1, bool mean_pool,
-    float* __restrict__ orow, int sl) {
+    out_t* __restrict__ orow, int sl) {
   constexpr int COLS = CodeUnit<BITS>::kCols;
   constexpr uint32_t kMask = (1u << BITS) - 1u;
   int code_bytes = D * BITS / 8;
@@ -397,21 +430,20 @@ __device__ __forceinline__ void pool_bag_nbit(
   }
   float s = 1.f;
   if (mean_pool && i1 > i0) s = 1.f / static_cast<float>(i1 - i0);
-  float4* o4 = reinterpret_cast<float4*>(orow);
 #pragma unroll
   for (int c = 0; c < CHUNKS; ++c) {
     int ui = c * LPS + sl;
     if (ui < n_units) {
 #pragma unroll
       for (int k = 0; k < COLS / 4; ++k)
-        o4[ui * (COLS / 4) + k] =
-            make_float4(acc[c][4 * k] * s, acc[c][4 * k + 1] * s, acc[c][4 * k + 2] * s,
-                        acc[c][4 * k + 3] * s);
+        Vec4<out_t>::store(orow, ui * (COLS / 4) + k,
+                           make_float4(acc[c][4 * k] * s, acc[c][4 * k + 1] * s,
+                                       acc[c][4 * k + 2] * s, acc[c][4 * k + 3] * s));
     }
   }
 }
 
-template <int LPS, int CHUNKS>
+template <typename out_t, int LPS, int CHUNKS>
 __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_pooled_nbit_kernel(
     const uint8_t* __restrict__ qweights,
     const int64_t* __restrict__ table_byte_offsets,  // [T]
@@ -422,7 +454,7 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_pooled_nbit_kernel(
     const int64_t* __restrict__ indices,
     const int64_t* __restrict__ offsets,  // [F*B+1]
     const float* __restrict__ psw, int F, int B, int64_t total_D, bool mean_pool,
-    float* __restrict__ out) {
+    out_t* __restrict__ out) {
   int sl = threadIdx.x % LPS;
   int64_t slot = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / LPS;
   int64_t n_slots = (static_cast<int64_t>(gridDim.x) * blockDim.x) / LPS;
@@ -434,18 +466,18 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_pooled_nbit_kernel(
     int bits = weight_bits[t];
     int D = dims[t];
     const uint8_t* tab = qweights + table_byte_offsets[t];
-    float* orow = out + static_cast<int64_t>(b) * total_D + d_out_offsets[f];
+    out_t* orow = out + static_cast<int64_t>(b) * total_D + d_out_offsets[f];
     int64_t i0 = offsets[bag], i1 = offsets[bag + 1];
     // bits is uniform within a slot; a wave diverges only where neighbouring
     // slots sit on a boundary between tables of different width. A slot
     // covers units [0, LPS*CHUNKS); lanes past this row's own unit count (a
     // narrow table in a module whose max is large) load and store nothing.
     if (bits == 8)
-      pool_bag_nbit<8, LPS, CHUNKS>(tab, D, indices, psw, i0, i1, mean_pool, orow, sl);
+      pool_bag_nbit<out_t, 8, LPS, CHUNKS>(tab, D, indices, psw, i0, i1, mean_pool, orow, sl);
     else if (bits == 4)
-      pool_bag_nbit<4, LPS, CHUNKS>(tab, D, indices, psw, i0, i1, mean_pool, orow, sl);
+      pool_bag_nbit<out_t, 4, LPS, CHUNKS>(tab, D, indices, psw, i0, i1, mean_pool, orow, sl);
     else
-      pool_bag_nbit<2, LPS, CHUNKS>(tab, D, indices, psw, i0, i1, mean_pool, orow, sl);
+      pool_bag_nbit<out_t, 2, LPS, CHUNKS>(tab, D, indices, psw, i0, i1, mean_pool, orow, sl);
   }
 }
 
@@ -481,34 +513,42 @@ at::Tensor tbe_forward_pooled_nbit(
     const at::Tensor& weight_bits, const at::Tensor& feat_table,
     const at::Tensor& d_out_offsets, const at::Tensor& indices, const at::Tensor& offsets,
     const at::Tensor& per_sample_weights, int64_t B, int64_t total_D, int64_t max_units,
-    bool mean_pool) {
+    bool mean_pool, int64_t output_dtype) {
   check_nbit_args(qweights, dims, weight_bits, max_units);
   // every table's D*bits % 32 == 0 makes D % 4 == 0, so rows store as float4
   TORCH_CHECK(total_D % 4 == 0, "n-bit TBE needs D*bits % 32 == 0 for every table");
+  auto out_st = quant_out_scalar_type(output_dtype, "tbe_forward_pooled_nbit");
   int F = feat_table.numel();
-  auto out = at::empty({B, total_D}, indices.options().dtype(at::kFloat));
+  auto out = at::empty({B, total_D}, indices.options().dtype(out_st));
   if (B == 0 || F == 0) return out;
   const float* psw_ptr =
       per_sample_weights.numel() > 0 ? per_sample_weights.data_ptr<float>() : nullptr;
   auto stream = q_stream();
   int grid = grid_for(static_cast<int64_t>(F) * B * nbit_lps(max_units), kBlockThreads);
-#define TBE_NB_LAUNCH(LPS, CHUNKS)                                                        \
-  hipLaunchKernelGGL((tbe_fwd_pooled_nbit_kernel<LPS, CHUNKS>), dim3(grid),               \
+#define TBE_NB_LAUNCH_T(out_t, LPS, CHUNKS)                                               \
+  hipLaunchKernelGGL((tbe_fwd_pooled_nbit_kernel<out_t, LPS, CHUNKS>), dim3(grid),        \
                      dim3(kBlockThreads), 0, stream, uvm_ptr<uint8_t>(qweights),           \
                      table_byte_offsets.data_ptr<int64_t>(), dims.data_ptr<int32_t>(),    \
                      weight_bits.data_ptr<int32_t>(), feat_table.data_ptr<int32_t>(),     \
                      d_out_offsets.data_ptr<int64_t>(), indices.data_ptr<int64_t>(),      \
                      offsets.data_ptr<int64_t>(), psw_ptr, F, (int)B, total_D, mean_pool, \
-                     out.data_ptr<float>())
+                     static_cast<out_t*>(out.data_ptr()))
+#define TBE_NB_LAUNCH(LPS, CHUNKS)                                  \
+  do {                                                              \
+    if (output_dtype == 1) TBE_NB_LAUNCH_T(__hip_bfloat16, LPS, CHUNKS); \
+    else if (output_dtype == 2) TBE_NB_LAUNCH_T(__half, LPS, CHUNKS);    \
+    else TBE_NB_LAUNCH_T(float, LPS, CHUNKS);                       \
+  } while (0)
   TBE_NBIT_DISPATCH(TBE_NB_LAUNCH, max_units);
 #undef TBE_NB_LAUNCH
+#undef TBE_NB_LAUNCH_T
   return out;
 }
 
 // sequence n-bit forward: out[n] = dequant(row(idx[n])), same lane mapping
-template <int BITS, int LPS, int CHUNKS>
+template <typename out_t, int BITS, int LPS, int CHUNKS>
 __device__ __forceinline__ void dequant_row_nbit(const uint8_t* __restrict__ row, int D,
-                                                 int D_out, float* __restrict__ orow, int sl) {
+                                                 int D_out, out_t* __restrict__ orow, int sl) {
   constexpr int COLS = CodeUnit<BITS>::kCols;
   constexpr uint32_t kMask = (1u << BITS) - 1u;
   const __half* sb = reinterpret_cast<const __half*>(row + D * BITS / 8);
@@ -516,7 +556,6 @@ __device__ __forceinline__ void dequant_row_nbit(const uint8_t* __restrict__ row
   float bias = __half2float(sb[1]);
   // an output row holds D_out columns: never store past it
   int n_units = min(D, D_out) / COLS;
-  float4* o4 = reinterpret_cast<float4*>(orow);
 #pragma unroll
   for (int c = 0; c < CHUNKS; ++c) {
     int ui = c * LPS + sl;
@@ -528,19 +567,19 @@ __device__ __forceinline__ void dequant_row_nbit(const uint8_t* __restrict__ row
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           v[j] = static_cast<float>((unit >> ((4 * k + j) * BITS)) & kMask) * scale + bias;
-        o4[ui * (COLS / 4) + k] = make_float4(v[0], v[1], v[2], v[3]);
+        Vec4<out_t>::store(orow, ui * (COLS / 4) + k, make_float4(v[0], v[1], v[2], v[3]));
       }
     }
   }
 }
 
-template <int LPS, int CHUNKS>
+template <typename out_t, int LPS, int CHUNKS>
 __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_seq_nbit_kernel(
     const uint8_t* __restrict__ qweights, const int64_t* __restrict__ table_byte_offsets,
     const int32_t* __restrict__ dims, const int32_t* __restrict__ weight_bits,
     const int32_t* __restrict__ feat_table, const int64_t* __restrict__ feat_val_offsets,
     const int64_t* __restrict__ indices, int F, int64_t N, int D_out,
-    float* __restrict__ out) {
+    out_t* __restrict__ out) {
   int sl = threadIdx.x % LPS;
   int64_t slot = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / LPS;
   int64_t n_slots = (static_cast<int64_t>(gridDim.x) * blockDim.x) / LPS;
@@ -551,10 +590,10 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_seq_nbit_kernel(
     int D = dims[t];
     const uint8_t* row =
         qweights + table_byte_offsets[t] + indices[n] * nbit_row_stride(D * bits / 8);
-    float* orow = out + n * D_out;
-    if (bits == 8) dequant_row_nbit<8, LPS, CHUNKS>(row, D, D_out, orow, sl);
-    else if (bits == 4) dequant_row_nbit<4, LPS, CHUNKS>(row, D, D_out, orow, sl);
-    else dequant_row_nbit<2, LPS, CHUNKS>(row, D, D_out, orow, sl);
+    out_t* orow = out + n * D_out;
+    if (bits == 8) dequant_row_nbit<out_t, 8, LPS, CHUNKS>(row, D, D_out, orow, sl);
+    else if (bits == 4) dequant_row_nbit<out_t, 4, LPS, CHUNKS>(row, D, D_out, orow, sl);
+    else dequant_row_nbit<out_t, 2, LPS, CHUNKS>(row, D, D_out, orow, sl);
   }
 }
 
@@ -562,25 +601,33 @@ at::Tensor tbe_forward_seq_nbit(
     const at::Tensor& qweights, const at::Tensor& table_byte_offsets, const at::Tensor& dims,
     const at::Tensor& weight_bits, const at::Tensor& feat_table,
     const at::Tensor& feat_val_offsets, const at::Tensor& indices, int64_t D_out,
-    int64_t max_units) {
+    int64_t max_units, int64_t output_dtype) {
   check_nbit_args(qweights, dims, weight_bits, max_units);
   TORCH_CHECK(D_out % 4 == 0 && D_out <= 4096,
               "n-bit TBE needs D*bits % 32 == 0 for every table");
+  auto out_st = quant_out_scalar_type(output_dtype, "tbe_forward_seq_nbit");
   int64_t N = indices.numel();
-  auto out = at::empty({N, D_out}, indices.options().dtype(at::kFloat));
+  auto out = at::empty({N, D_out}, indices.options().dtype(out_st));
   if (N == 0) return out;
   int F = feat_table.numel();
   auto stream = q_stream();
   int grid = grid_for(N * nbit_lps(max_units), kBlockThreads);
-#define TBE_NBS_LAUNCH(LPS, CHUNKS)                                                       \
-  hipLaunchKernelGGL((tbe_fwd_seq_nbit_kernel<LPS, CHUNKS>), dim3(grid),                  \
+#define TBE_NBS_LAUNCH_T(out_t, LPS, CHUNKS)                                              \
+  hipLaunchKernelGGL((tbe_fwd_seq_nbit_kernel<out_t, LPS, CHUNKS>), dim3(grid),           \
                      dim3(kBlockThreads), 0, stream, uvm_ptr<uint8_t>(qweights),           \
                      table_byte_offsets.data_ptr<int64_t>(), dims.data_ptr<int32_t>(),    \
                      weight_bits.data_ptr<int32_t>(), feat_table.data_ptr<int32_t>(),     \
                      feat_val_offsets.data_ptr<int64_t>(), indices.data_ptr<int64_t>(), F, \
-                     N, (int)D_out, out.data_ptr<float>())
+                     N, (int)D_out, static_cast<out_t*>(out.data_ptr()))
+#define TBE_NBS_LAUNCH(LPS, CHUNKS)                                  \
+  do {                                                               \
+    if (output_dtype == 1) TBE_NBS_LAUNCH_T(__hip_bfloat16, LPS, CHUNKS); \
+    else if (output_dtype == 2) TBE_NBS_LAUNCH_T(__half, LPS, CHUNKS);    \
+    else TBE_NBS_LAUNCH_T(float, LPS, CHUNKS);                       \
+  } while (0)
   TBE_NBIT_DISPATCH(TBE_NBS_LAUNCH, max_units);
 #undef TBE_NBS_LAUNCH
+#undef TBE_NBS_LAUNCH_T
 #undef TBE_NBIT_DISPATCH
   return out;
 }

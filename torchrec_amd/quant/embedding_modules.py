@@ -37,6 +37,8 @@ from torchrec_amd.sparse.jagged_tensor import JaggedTensor, KeyedJaggedTensor, K
 _QUANT_DATA_TYPES = (DataType.INT8, DataType.INT4, DataType.INT2)
 # output columns one lane of the n-bit kernels owns, by width (quant_tbe.hip: CodeUnit)
 _LANE_COLS = {8: 4, 4: 8, 2: 8}
+# output_dtype -> the ops' code (the training TBE's: ops/tbe.py)
+_OUT_DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
 def quant_data_type(data_type: object) -> DataType:
@@ -158,7 +160,8 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
     offsets and per-table width (``weight_dtypes``: INT8/INT4/INT2, None = all
     INT8). GPU path = tbe_forward_pooled_int8 when every table is INT8, else
     tbe_forward_pooled_nbit (one launch for mixed widths); CPU path = dequant
-    reference."""
+    reference. ``output_dtype`` (fp32 / bf16 / fp16) is the dtype of every
+    lookup's result: the arithmetic is fp32 and the value is rounded once."""
 
     def __init__(
         self,
@@ -168,8 +171,16 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         device: Optional[torch.device] = None,
         location: str = "device",  # "device" (HBM) | "managed" (pinned host, QUANT_UVM)
         weight_dtypes: Optional[List[DataType]] = None,
+        output_dtype: torch.dtype = torch.float32,
     ) -> None:
         super().__init__()
+        if output_dtype not in _OUT_DTYPE_CODE:
+            raise ValueError(
+                f"output_dtype must be torch.float32, torch.bfloat16 or torch.float16, "
+                f"got {output_dtype}"
+            )
+        self.output_dtype = output_dtype
+        self._out_dtype_code = _OUT_DTYPE_CODE[output_dtype]
         device = device or torch.device("cpu")
         self._uvm = location == "managed" and device.type == "cuda"
         qdevice = torch.device("cpu") if self._uvm else device
@@ -276,6 +287,7 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
                     self._total_D,
                     self._max_units,
                     self.pooling == PoolingType.MEAN,
+                    self._out_dtype_code,
                 )
             return torch.ops.trec_amd.tbe_forward_pooled_int8(
                 self.qweights,
@@ -290,6 +302,7 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
                 self._total_D,
                 self._max_D,
                 self.pooling == PoolingType.MEAN,
+                self._out_dtype_code,
             )
         # CPU reference
         outs = []
@@ -302,17 +315,31 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
                 if per_sample_weights is not None
                 else None
             )
+            mean = self.pooling == PoolingType.MEAN
+            if mean and pw is not None:
+                # embedding_bag has no weighted mean; the kernels compute the
+                # weighted sum over the bag length
+                pooled = torch.nn.functional.embedding_bag(
+                    idx, w, off, mode="sum", per_sample_weights=pw, include_last_offset=True
+                )
+                n = (off[1:] - off[:-1]).clamp(min=1).to(pooled.dtype)
+                outs.append(pooled / n.unsqueeze(1))
+                continue
             outs.append(
                 torch.nn.functional.embedding_bag(
                     idx,
                     w,
                     off,
-                    mode="mean" if self.pooling == PoolingType.MEAN else "sum",
+                    mode="mean" if mean else "sum",
                     per_sample_weights=pw,
                     include_last_offset=True,
                 )
             )
-        return torch.cat(outs, dim=1)
+        return self.to_output_dtype(torch.cat(outs, dim=1))
+
+    def to_output_dtype(self, x: torch.Tensor) -> torch.Tensor:
+        """The one rounding of an fp32 CPU-reference result to ``output_dtype``."""
+        return x if x.dtype == self.output_dtype else x.to(self.output_dtype)
 
     @torch.no_grad()
     def forward_sequence(
@@ -332,6 +359,7 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
                 indices,
                 dim,
                 self._max_units,
+                self._out_dtype_code,
             )
         return torch.ops.trec_amd.tbe_forward_seq_int8(
             self.qweights,
@@ -342,6 +370,7 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
             indices,
             dim,
             self._max_D,
+            self._out_dtype_code,
         )
 
 
@@ -370,6 +399,7 @@ class EmbeddingBagCollection(nn.Module):
         super().__init__()
         self._embedding_bag_configs = tables
         self._is_weighted = is_weighted
+        self._output_dtype = output_dtype
         self._feature_names = [f for t in tables for f in t.feature_names]
         self._lengths_per_embedding = [t.embedding_dim for t in tables for _ in t.feature_names]
         poolings = {t.pooling for t in tables}
@@ -380,6 +410,7 @@ class EmbeddingBagCollection(nn.Module):
             pooling=next(iter(poolings)) if poolings else PoolingType.SUM,
             device=device,
             weight_dtypes=[quant_data_type(t.data_type) for t in tables],
+            output_dtype=output_dtype,
         )
 
     @classmethod
@@ -408,6 +439,7 @@ class EmbeddingBagCollection(nn.Module):
             ],
             is_weighted=module.is_weighted(),
             device=device,
+            output_dtype=output_dtype,
         )
         for i, t in enumerate(tables):
             q._tbe.load_float_table(i, module.embedding_bags[t.name].weight.detach())
@@ -418,6 +450,9 @@ class EmbeddingBagCollection(nn.Module):
 
     def is_weighted(self) -> bool:
         return self._is_weighted
+
+    def output_dtype(self) -> torch.dtype:
+        return self._output_dtype
 
     def forward(self, features: KeyedJaggedTensor) -> KeyedTensor:
         if features.keys() != self._feature_names:
@@ -448,6 +483,7 @@ class EmbeddingCollection(nn.Module):
     ) -> None:
         super().__init__()
         self._embedding_configs = tables
+        self._output_dtype = output_dtype
         self._feature_names = [f for t in tables for f in t.feature_names]
         dims = {t.embedding_dim for t in tables}
         assert len(dims) <= 1
@@ -457,6 +493,7 @@ class EmbeddingCollection(nn.Module):
             feature_table_map=[i for i, t in enumerate(tables) for _ in t.feature_names],
             device=device,
             weight_dtypes=[quant_data_type(t.data_type) for t in tables],
+            output_dtype=output_dtype,
         )
 
     @classmethod
@@ -475,13 +512,16 @@ class EmbeddingCollection(nn.Module):
             )
             for t in module.embedding_configs()
         ]
-        q = cls(tables=tables)
+        q = cls(tables=tables, output_dtype=output_dtype)
         for i, t in enumerate(tables):
             q._tbe.load_float_table(i, module.embeddings[t.name].weight.detach())
         return q
 
     def embedding_configs(self) -> List[EmbeddingConfig]:
         return self._embedding_configs
+
+    def output_dtype(self) -> torch.dtype:
+        return self._output_dtype
 
     @torch.no_grad()
     def forward(self, features: KeyedJaggedTensor) -> Dict[str, JaggedTensor]:
@@ -504,6 +544,7 @@ class EmbeddingCollection(nn.Module):
                 idx = features.values()[int(offsets[f * B]) : int(offsets[(f + 1) * B])]
                 rows_l.append(w[idx])
             rows = torch.cat(rows_l, dim=0) if rows_l else torch.empty(0, self._dim)
+            rows = tbe.to_output_dtype(rows)
         out: Dict[str, JaggedTensor] = {}
         opk = features.offset_per_key()
         lengths = features.lengths()
