@@ -138,10 +138,12 @@ def bench_col_sum(M=8192, N=1024):
 
 
 def bench_quant_tbe(B=8192, D=128, tables=26, rows=100_000, weight_dtype=None, repeats=1,
-                    output_dtype=torch.float32, emit=True):
+                    output_dtype=torch.float32, emit=True, mixed_kernel=False):
     """Quantized inference TBE forward at ``weight_dtype`` (default INT8) vs
     the fp32 training TBE forward, writing ``output_dtype``. Returns the
-    ``repeats`` timings in us; ``emit=False`` leaves the printing to the caller."""
+    ``repeats`` timings in us; ``emit=False`` leaves the printing to the caller.
+    ``mixed_kernel`` sends an all-INT8 module through the mixed-format n-bit
+    kernel (its 8-bit arm) instead of the INT8 kernel."""
     from torchrec_amd.modules.embedding_configs import DATA_TYPE_NUM_BITS, DataType
     from torchrec_amd.quant.embedding_modules import (
         QuantTableBatchedEmbeddingBags,
@@ -159,6 +161,8 @@ def bench_quant_tbe(B=8192, D=128, tables=26, rows=100_000, weight_dtype=None, r
     )
     for i in range(tables):
         q.load_float_table(i, torch.randn(rows, D, device="cuda"))
+    if mixed_kernel:
+        q._all_int8 = False
     F = tables
     indices = torch.randint(0, rows, (F * B,)).cuda()
     offsets = torch.arange(F * B + 1, dtype=torch.int64).cuda()
@@ -232,11 +236,43 @@ def bench_quant_out_suite(B=8192, D=128, tables=26):
                  within_noise_or_faster=bool(sorted(t)[1] <= med + spread))
 
 
+def bench_quant_fp8_suite(B=8192, D=128, tables=26):
+    """FP8 rows against INT8 rows, the same bytes per row and the same output
+    write. Per output dtype: INT8 five times (median + max-min spread = the
+    noise margin of this run), then FP8 three times, then the same INT8 rows
+    three times through the mixed-format kernel FP8 runs in (its 8-bit arm),
+    which tells the cost of that kernel from the cost of the FP8 arm. All in
+    this process."""
+    from torchrec_amd.modules.embedding_configs import DataType
+
+    for out in (torch.float32, torch.bfloat16, torch.float16):
+        int8 = bench_quant_tbe(
+            B, D, tables, weight_dtype=DataType.INT8, repeats=5, output_dtype=out, emit=False
+        )
+        med, spread = sorted(int8)[2], max(int8) - min(int8)
+        fp8 = bench_quant_tbe(
+            B, D, tables, weight_dtype=DataType.FP8, repeats=3, output_dtype=out, emit=False
+        )
+        int8_mixed = bench_quant_tbe(
+            B, D, tables, weight_dtype=DataType.INT8, repeats=3, output_dtype=out, emit=False,
+            mixed_kernel=True,
+        )
+        print(json.dumps({
+            "bench": "quant_tbe_fwd_fp8_vs_int8",
+            "output_dtype": str(out).replace("torch.", ""), "B": B, "tables": tables, "D": D,
+            "fp8_us": round(sorted(fp8)[1], 1), "fp8_us_runs": [round(t, 1) for t in fp8],
+            "int8_median_us": round(med, 1), "int8_us_runs": [round(t, 1) for t in int8],
+            "int8_spread_us": round(spread, 1),
+            "int8_mixed_kernel_us_runs": [round(t, 1) for t in int8_mixed],
+            "within_noise_or_faster": bool(sorted(fp8)[1] <= med + spread),
+        }))
+
+
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--suite", default="all",
                    choices=["all", "tbe", "tbe_sweep", "interaction", "sort",
-                            "col_sum", "quant", "quant_out"])
+                            "col_sum", "quant", "quant_out", "quant_fp8"])
     a = p.parse_args()
     assert torch.cuda.is_available(), "run on a GPU box"
     if a.suite in ("all", "tbe"):
@@ -260,3 +296,5 @@ if __name__ == "__main__":
         bench_quant_suite()
     if a.suite == "quant_out":
         bench_quant_out_suite()
+    if a.suite == "quant_fp8":
+        bench_quant_fp8_suite()

@@ -1,10 +1,13 @@
-"""Quantized inference end to end: train (briefly) -> int8-quantize ->
-shard for inference -> serve through the native batching runtime.
+"""Quantized inference end to end: train (briefly) -> quantize (INT8 by
+default) -> shard for inference -> serve through the native batching runtime.
 
-Run (1 GPU):  python examples/quantized_inference.py
+Run (1 GPU):  python examples/quantized_inference.py [--weight-dtype FP8]
+``--weight-dtype`` is INT8, INT4, INT2 or FP8 (e4m3fn codes with a rowwise
+scale: the bytes of INT8, a relative instead of an absolute error).
 CPU works too (reference dequant path).
 """
 
+import argparse
 import os
 import sys
 
@@ -14,12 +17,15 @@ import torch
 
 from torchrec_amd.inference.modules import quantize_inference_model
 from torchrec_amd.models.dlrm import DLRM
-from torchrec_amd.modules.embedding_configs import EmbeddingBagConfig
+from torchrec_amd.modules.embedding_configs import DataType, EmbeddingBagConfig
 from torchrec_amd.modules.embedding_modules import EmbeddingBagCollection
 from torchrec_amd.sparse.jagged_tensor import KeyedJaggedTensor
 
 
 def main() -> None:
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--weight-dtype", default="INT8", choices=["INT8", "INT4", "INT2", "FP8"])
+    args = parser.parse_args()
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     keys = [f"cat_{i}" for i in range(4)]
     rows = [1000, 500, 800, 600]
@@ -38,8 +44,8 @@ def main() -> None:
         dense_arch_layer_sizes=[16, 16],
         over_arch_layer_sizes=[16, 1],
     )
-    # int8-quantize the sparse arch for serving
-    qmodel = quantize_inference_model(model)
+    # quantize the sparse arch for serving
+    qmodel = quantize_inference_model(model, weight_dtype=DataType[args.weight_dtype])
     qmodel = qmodel.to(device)
 
     B = 8

@@ -54,7 +54,7 @@ class ShardedTableLocal:
     full_dim: int = 0
     full_rows: int = 0
     use_sum_kernel: bool = False  # RW mean: kernel sums, divisor applied later
-    # weights precision (DataType.name): FP32/FP16/BF16; INT8/INT4/INT2 for quant
+    # weights precision (DataType.name): FP32/FP16/BF16; INT8/INT4/INT2/FP8 for quant
     data_type: str = "FP32"
 
 

@@ -3,7 +3,7 @@
 Reference parity: torchrec/distributed/quant_embedding.py
 (ShardedQuantEmbeddingCollection) — the training sequence dists (feature a2a
 in, per-row embedding a2a out) reused over the rowwise-quantized
-(INT8/INT4/INT2 per table) sequence lookups."""
+(INT8/INT4/INT2/FP8 per table) sequence lookups."""
 
 from __future__ import annotations
 

@@ -4,7 +4,7 @@ Reference parity: torchrec/distributed/quant_embeddingbag.py
 (ShardedQuantEmbeddingBagCollection) and the infer shardings
 (tw_sharding.py:543 InferTwEmbeddingSharding): the training dists are reused
 (one process per GPU over RCCL/xGMI); lookups run the quantized TBE at each
-table's own width (INT8/INT4/INT2).
+table's own format (INT8/INT4/INT2/FP8).
 """
 
 from __future__ import annotations

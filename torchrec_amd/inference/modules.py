@@ -32,8 +32,8 @@ def quantize_inference_model(
 ) -> nn.Module:
     """Swap float embedding modules for rowwise-quantized ones in-place
     (reference inference/modules.py:372). Tables are packed at
-    ``weight_dtype`` (INT8/INT4/INT2) unless ``per_table_weight_dtype`` names
-    another width for them."""
+    ``weight_dtype`` (INT8/INT4/INT2/FP8) unless ``per_table_weight_dtype``
+    names another format for them."""
     mapping = quantization_mapping or {
         FloatEBC: QuantEBC,
         FloatEC: QuantEC,

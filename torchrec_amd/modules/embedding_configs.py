@@ -32,6 +32,7 @@ class DataType(Enum):
     INT8 = "INT8"
     INT4 = "INT4"
     INT2 = "INT2"
+    FP8 = "FP8"  # e4m3fn codes with a rowwise fp16 scale (quantized inference)
 
     def __str__(self) -> str:
         return self.value
@@ -44,6 +45,7 @@ DATA_TYPE_NUM_BITS: Dict[DataType, int] = {
     DataType.INT8: 8,
     DataType.INT4: 4,
     DataType.INT2: 2,
+    DataType.FP8: 8,
 }
 
 
@@ -55,6 +57,7 @@ def data_type_to_dtype(data_type: DataType) -> torch.dtype:
         DataType.INT8: torch.uint8,
         DataType.INT4: torch.uint8,
         DataType.INT2: torch.uint8,
+        DataType.FP8: torch.uint8,
     }[data_type]
 
 

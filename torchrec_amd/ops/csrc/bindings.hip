@@ -124,6 +124,7 @@ at::Tensor tbe_forward_seq_int8(const at::Tensor& qweights,
                                 const at::Tensor& feat_val_offsets, const at::Tensor& indices,
                                 int64_t D_out, int64_t max_D, int64_t output_dtype);
 at::Tensor quantize_rowwise_nbit(const at::Tensor& weights, int64_t bits);
+at::Tensor quantize_rowwise_fp8(const at::Tensor& weights);
 at::Tensor tbe_forward_pooled_nbit(const at::Tensor& qweights,
                                    const at::Tensor& table_byte_offsets, const at::Tensor& dims,
                                    const at::Tensor& weight_bits, const at::Tensor& feat_table,
@@ -270,6 +271,7 @@ TORCH_LIBRARY(trec_amd, m) {
       " Tensor feat_table, Tensor feat_val_offsets, Tensor indices, int D_out, int max_D,"
       " int output_dtype=0) -> Tensor");
   m.def("quantize_rowwise_nbit(Tensor weights, int bits) -> Tensor");
+  m.def("quantize_rowwise_fp8(Tensor weights) -> Tensor");
   m.def(
       "tbe_forward_pooled_nbit(Tensor qweights, Tensor table_byte_offsets, Tensor dims,"
       " Tensor weight_bits, Tensor feat_table, Tensor d_out_offsets, Tensor indices,"
@@ -331,6 +333,7 @@ TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
   m.impl("tbe_forward_pooled_int8", trec_amd::tbe_forward_pooled_int8);
   m.impl("tbe_forward_seq_int8", trec_amd::tbe_forward_seq_int8);
   m.impl("quantize_rowwise_nbit", trec_amd::quantize_rowwise_nbit);
+  m.impl("quantize_rowwise_fp8", trec_amd::quantize_rowwise_fp8);
   m.impl("tbe_forward_pooled_nbit", trec_amd::tbe_forward_pooled_nbit);
   m.impl("tbe_forward_seq_nbit", trec_amd::tbe_forward_seq_nbit);
   m.impl("col_sum", trec_amd::col_sum);

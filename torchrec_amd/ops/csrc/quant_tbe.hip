@@ -1,5 +1,5 @@
 // Rowwise-quantized inference TBE for MI355X (gfx950): the INT8 kernels, and
-// below them the n-bit (INT8/INT4/INT2, mixed per table) kernels.
+// below them the n-bit (INT8/INT4/INT2 and FP8, mixed per table) kernels.
 //
 // MI355X-native equivalent of the reference's IntNBitTableBatchedEmbeddingBags
 // (reference torchrec/distributed/quant_embedding_kernel.py:237; kernel spec:
@@ -8,6 +8,19 @@
 //
 // Row format: [uint8 x D][fp16 scale][fp16 bias], padded to 16 B so rows load
 // as uchar4/uint4. Dequant: w = q * scale + bias.
+//
+// FP8 row format: [e4m3fn codes: D bytes][fp16 scale][2 zero bytes][zero
+// padding], stride round_up(D + 4, 16) (the INT8 stride), D % 4 == 0. The
+// codes are OCP e4m3fn, the format gfx950 converts natively (NOT MI300's
+// e4m3fnuz). No bias: e4m3 is signed.
+//   amax    = max |x| over the row
+//   scale_h = the smallest fp16 >= amax / 448 (round UP, so |x| / scale_h
+//             <= 448 and nothing saturates); amax == 0 gives scale_h = 0 and
+//             all codes 0
+//   code    = e4m3fn_rne(clamp(x / float(scale_h), -448, 448)); the NaN
+//             codes 0x7f / 0xff are never produced
+//   dequant = decode(code) * float(scale_h), in fp32
+// Inputs are assumed finite with amax <= 448 * 65504.
 
 #include <torch/extension.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -282,7 +295,7 @@ at::Tensor tbe_forward_seq_int8(
 }
 
 // ===========================================================================
-// n-bit rows (INT8 / INT4 / INT2), mixed per table in one launch.
+// n-bit rows (INT8 / INT4 / INT2, and FP8), mixed per table in one launch.
 //
 // Row = [codes: D*bits/8 B][fp16 scale][fp16 bias][zero pad], stride rounded
 // up to 16 B; D*bits % 32 == 0 so a row is a whole number of 32-bit code
@@ -373,6 +386,84 @@ at::Tensor quantize_rowwise_nbit(const at::Tensor& weights, int64_t bits) {
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// fp32 [R, D] -> FP8 (e4m3fn) rowwise-scaled rows (format: top of this file)
+// ---------------------------------------------------------------------------
+
+// smallest fp16 >= v, for finite v >= 0: round to nearest, then step up once if
+// that fell short. Plain arithmetic (the CPU reference does the same), no
+// rounding-mode intrinsic.
+__device__ __forceinline__ __half half_round_up(float v) {
+  __half h = __float2half(v);
+  if (__half2float(h) < v) {
+    uint16_t b = __half_as_ushort(h);
+    h = __ushort_as_half(static_cast<uint16_t>(b + 1));
+  }
+  return h;
+}
+
+__device__ __forceinline__ float fp8_prescale(float x, float scale) {
+  return fminf(fmaxf(x / scale, -448.f), 448.f);
+}
+
+__global__ void quantize_rowwise_fp8_kernel(const float* __restrict__ w, int64_t R, int D,
+                                            int64_t stride, uint8_t* __restrict__ out) {
+  // one wave per row
+  int64_t wave = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWaveSize;
+  int64_t n_waves = (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWaveSize;
+  int l = lane_id();
+  int n_words = D / 4;
+  for (int64_t r = wave; r < R; r += n_waves) {
+    const float* row = w + r * D;
+    float amax = 0.f;
+    for (int d = l; d < D; d += kWaveSize) amax = fmaxf(amax, fabsf(row[d]));
+#pragma unroll
+    for (int off = kWaveSize / 2; off > 0; off >>= 1)
+      amax = fmaxf(amax, __shfl_xor(amax, off, kWaveSize));
+    __half scale_h = half_round_up(amax / 448.f);
+    // codes are taken against the STORED scale
+    float scale = __half2float(scale_h);
+    uint32_t* owords = reinterpret_cast<uint32_t*>(out + r * stride);
+    for (int wi = l; wi < n_words; wi += kWaveSize) {
+      int word = 0;
+      if (scale != 0.f) {
+        const float* x = row + wi * 4;
+        // packed convert: two floats -> two e4m3fn bytes (round to nearest
+        // even) into the low / high half of the word
+        word = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_prescale(x[0], scale),
+                                               fp8_prescale(x[1], scale), word, false);
+        word = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_prescale(x[2], scale),
+                                               fp8_prescale(x[3], scale), word, true);
+      }
+      owords[wi] = static_cast<uint32_t>(word);
+    }
+    // scale + the two reserved zero bytes are one word
+    if (l == 0) owords[n_words] = static_cast<uint32_t>(__half_as_ushort(scale_h));
+    int n_pad = static_cast<int>(stride / 4) - n_words - 1;
+    for (int k = l; k < n_pad; k += kWaveSize) owords[n_words + 1 + k] = 0u;
+  }
+}
+
+at::Tensor quantize_rowwise_fp8(const at::Tensor& weights) {
+  TORCH_CHECK(weights.is_cuda() && weights.dim() == 2 && weights.scalar_type() == at::kFloat);
+  int64_t R = weights.size(0);
+  int D = weights.size(1);
+  TORCH_CHECK(D > 0 && D % 4 == 0, "quantize_rowwise_fp8: D (", D, ") must be a multiple of 4");
+  int64_t stride = nbit_row_stride(D);
+  auto out = at::empty({R, stride}, weights.options().dtype(at::kByte));
+  if (R == 0) return out;
+  auto w = weights.contiguous();
+  hipLaunchKernelGGL(quantize_rowwise_fp8_kernel,
+                     dim3(grid_for(R * kWaveSize, kBlockThreads)), dim3(kBlockThreads), 0,
+                     q_stream(), w.data_ptr<float>(), R, D, stride, out.data_ptr<uint8_t>());
+  return out;
+}
+
+// Per-table format code, the values of weight_bits[t]: 8 / 4 / 2 are the
+// integer widths; FP8 rows are 8 bits wide too, so they carry a code of
+// their own whose low byte is still the width.
+constexpr int kFormatFp8 = 0x108;
+
 // Lane mapping. A lane owns one code unit of every row per chunk: the 32-bit
 // word at INT8 (4 columns) and INT4 (8 columns), the 16-bit half-word at INT2
 // (8 columns). A lane that owned a whole INT2 word would store four float4 at
@@ -381,8 +472,10 @@ at::Tensor quantize_rowwise_nbit(const at::Tensor& weights, int64_t bits) {
 // With a 2-byte out_t the 8 columns are 16 B, but a segment start is only a
 // multiple of 4 elements (a D=20 table in front puts it at byte 40), so they
 // go out as two 8-byte quads like the fp32 pair, never as one 16-byte store.
-template <int BITS>
+// An FP8 row maps like an INT8 row: the 32-bit word, 4 columns.
+template <int FMT>
 struct CodeUnit {
+  static constexpr int BITS = FMT & 0xff;
   static constexpr int kCols = BITS == 8 ? 4 : 8;  // output columns per lane
   static constexpr int kBits = kCols * BITS;       // 32, 32, 16
   __device__ static __forceinline__ uint32_t load(const uint8_t* __restrict__ row, int ui) {
@@ -391,14 +484,15 @@ struct CodeUnit {
   }
 };
 
-// One lane's share of a bag. BITS is a template parameter so the accumulators
-// stay in registers; the caller switches on the bag's table.
-template <typename out_t, int BITS, int LPS, int CHUNKS>
+// One lane's share of a bag. The format is a template parameter so the
+// accumulators stay in registers; the caller switches on the bag's table.
+template <typename out_t, int FMT, int LPS, int CHUNKS>
 __device__ __forceinline__ void pool_bag_nbit(
     const uint8_t* __restrict__ tab, int D, const int64_t* __restrict__ indices,
     const float* __restrict__ psw, int64_t i0, int64_t i1, bool mean_pool,
     out_t* __restrict__ orow, int sl) {
-  constexpr int COLS = CodeUnit<BITS>::kCols;
+  constexpr int BITS = CodeUnit<FMT>::BITS;
+  constexpr int COLS = CodeUnit<FMT>::kCols;
   constexpr uint32_t kMask = (1u << BITS) - 1u;
   int code_bytes = D * BITS / 8;
   int n_units = D / COLS;
@@ -413,17 +507,27 @@ __device__ __forceinline__ void pool_bag_nbit(
     // same address across the slot: one broadcast load
     const __half* sb = reinterpret_cast<const __half*>(row + code_bytes);
     float scale = __half2float(sb[0]);
-    float bias = __half2float(sb[1]);
+    float bias = __half2float(sb[1]);  // FP8: the reserved bytes, unused
     float w = psw ? psw[i] : 1.f;
 #pragma unroll
     for (int c = 0; c < CHUNKS; ++c) {
       int ui = c * LPS + sl;
       if (ui < n_units) {
-        uint32_t unit = CodeUnit<BITS>::load(row, ui);
+        uint32_t unit = CodeUnit<FMT>::load(row, ui);
+        if constexpr (FMT == kFormatFp8) {
+          // packed convert: the low / high two e4m3fn bytes -> two floats
+          auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(unit), false);
+          auto hi = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(unit), true);
+          acc[c][0] += w * (lo[0] * scale);
+          acc[c][1] += w * (lo[1] * scale);
+          acc[c][2] += w * (hi[0] * scale);
+          acc[c][3] += w * (hi[1] * scale);
+        } else {
 #pragma unroll
-        for (int j = 0; j < COLS; ++j) {
-          float q = static_cast<float>((unit >> (j * BITS)) & kMask);
-          acc[c][j] += w * (q * scale + bias);
+          for (int j = 0; j < COLS; ++j) {
+            float q = static_cast<float>((unit >> (j * BITS)) & kMask);
+            acc[c][j] += w * (q * scale + bias);
+          }
         }
       }
     }
@@ -448,7 +552,7 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_pooled_nbit_kernel(
     const uint8_t* __restrict__ qweights,
     const int64_t* __restrict__ table_byte_offsets,  // [T]
     const int32_t* __restrict__ dims,                // [T]
-    const int32_t* __restrict__ weight_bits,         // [T] 8 / 4 / 2
+    const int32_t* __restrict__ weight_bits,         // [T] 8 / 4 / 2 / kFormatFp8
     const int32_t* __restrict__ feat_table,          // [F]
     const int64_t* __restrict__ d_out_offsets,       // [F+1]
     const int64_t* __restrict__ indices,
@@ -476,13 +580,16 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_pooled_nbit_kernel(
       pool_bag_nbit<out_t, 8, LPS, CHUNKS>(tab, D, indices, psw, i0, i1, mean_pool, orow, sl);
     else if (bits == 4)
       pool_bag_nbit<out_t, 4, LPS, CHUNKS>(tab, D, indices, psw, i0, i1, mean_pool, orow, sl);
+    else if (bits == kFormatFp8)
+      pool_bag_nbit<out_t, kFormatFp8, LPS, CHUNKS>(tab, D, indices, psw, i0, i1, mean_pool,
+                                                    orow, sl);
     else
       pool_bag_nbit<out_t, 2, LPS, CHUNKS>(tab, D, indices, psw, i0, i1, mean_pool, orow, sl);
   }
 }
 
 // slot width / chunk count from the widest row in lane units (CodeUnit:
-// D/4 at INT8, D/8 at INT4 and INT2)
+// D/4 at INT8 and FP8, D/8 at INT4 and INT2)
 #define TBE_NBIT_DISPATCH(LAUNCH, max_units)                    \
   do {                                                          \
     if ((max_units) <= 8) LAUNCH(8, 1);                         \
@@ -504,7 +611,7 @@ static void check_nbit_args(const at::Tensor& qweights, const at::Tensor& dims,
   TORCH_CHECK(weight_bits.scalar_type() == at::kInt && weight_bits.numel() == dims.numel(),
               "weight_bits must be int32 [T]");
   TORCH_CHECK(max_units >= 1 && max_units <= 512,
-              "n-bit TBE rows must be 1..512 lane units (D/4 at INT8, D/8 at INT4/INT2), got ",
+              "n-bit TBE rows must be 1..512 lane units (D/4 at INT8/FP8, D/8 at INT4/INT2), got ",
               max_units);
 }
 
@@ -546,10 +653,11 @@ at::Tensor tbe_forward_pooled_nbit(
 }
 
 // sequence n-bit forward: out[n] = dequant(row(idx[n])), same lane mapping
-template <typename out_t, int BITS, int LPS, int CHUNKS>
+template <typename out_t, int FMT, int LPS, int CHUNKS>
 __device__ __forceinline__ void dequant_row_nbit(const uint8_t* __restrict__ row, int D,
                                                  int D_out, out_t* __restrict__ orow, int sl) {
-  constexpr int COLS = CodeUnit<BITS>::kCols;
+  constexpr int BITS = CodeUnit<FMT>::BITS;
+  constexpr int COLS = CodeUnit<FMT>::kCols;
   constexpr uint32_t kMask = (1u << BITS) - 1u;
   const __half* sb = reinterpret_cast<const __half*>(row + D * BITS / 8);
   float scale = __half2float(sb[0]);
@@ -560,14 +668,21 @@ __device__ __forceinline__ void dequant_row_nbit(const uint8_t* __restrict__ row
   for (int c = 0; c < CHUNKS; ++c) {
     int ui = c * LPS + sl;
     if (ui < n_units) {
-      uint32_t unit = CodeUnit<BITS>::load(row, ui);
+      uint32_t unit = CodeUnit<FMT>::load(row, ui);
+      if constexpr (FMT == kFormatFp8) {
+        auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(unit), false);
+        auto hi = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(unit), true);
+        Vec4<out_t>::store(orow, ui, make_float4(lo[0] * scale, lo[1] * scale, hi[0] * scale,
+                                                 hi[1] * scale));
+      } else {
 #pragma unroll
-      for (int k = 0; k < COLS / 4; ++k) {
-        float v[4];
+        for (int k = 0; k < COLS / 4; ++k) {
+          float v[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-          v[j] = static_cast<float>((unit >> ((4 * k + j) * BITS)) & kMask) * scale + bias;
-        Vec4<out_t>::store(orow, ui * (COLS / 4) + k, make_float4(v[0], v[1], v[2], v[3]));
+          for (int j = 0; j < 4; ++j)
+            v[j] = static_cast<float>((unit >> ((4 * k + j) * BITS)) & kMask) * scale + bias;
+          Vec4<out_t>::store(orow, ui * (COLS / 4) + k, make_float4(v[0], v[1], v[2], v[3]));
+        }
       }
     }
   }
@@ -589,10 +704,12 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_seq_nbit_kernel(
     int bits = weight_bits[t];
     int D = dims[t];
     const uint8_t* row =
-        qweights + table_byte_offsets[t] + indices[n] * nbit_row_stride(D * bits / 8);
+        qweights + table_byte_offsets[t] + indices[n] * nbit_row_stride(D * (bits & 0xff) / 8);
     out_t* orow = out + n * D_out;
     if (bits == 8) dequant_row_nbit<out_t, 8, LPS, CHUNKS>(row, D, D_out, orow, sl);
     else if (bits == 4) dequant_row_nbit<out_t, 4, LPS, CHUNKS>(row, D, D_out, orow, sl);
+    else if (bits == kFormatFp8)
+      dequant_row_nbit<out_t, kFormatFp8, LPS, CHUNKS>(row, D, D_out, orow, sl);
     else dequant_row_nbit<out_t, 2, LPS, CHUNKS>(row, D, D_out, orow, sl);
   }
 }

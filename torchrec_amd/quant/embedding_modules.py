@@ -1,4 +1,4 @@
-"""Quantized (rowwise INT8 / INT4 / INT2) inference embedding modules.
+"""Quantized (rowwise INT8 / INT4 / INT2 / FP8) inference embedding modules.
 
 Reference parity: torchrec/quant/embedding_modules.py
 (quant EmbeddingBagCollection :346 with from_float / quantize_state_dict
@@ -10,6 +10,21 @@ Packed row, for bits in {8, 4, 2}: ``[codes: D*bits/8 B][fp16 scale]
 byte ``e*bits // 8`` at bit ``(e*bits) % 8``, low bits first. ``w = q * scale
 + bias``. The width is a per-table choice (``EmbeddingBagConfig.data_type``);
 a module whose tables are all INT8 runs exactly the INT8 kernels.
+
+FP8 row (``DataType.FP8``): ``[e4m3fn codes: D bytes][fp16 scale][2 zero
+bytes][zero padding]``, stride ``round_up(D + 4, 16)`` (the INT8 stride),
+``D % 4 == 0``. The codes are OCP ``e4m3fn`` (``torch.float8_e4m3fn``), which
+gfx950 converts natively, not MI300's ``e4m3fnuz``. There is no bias: e4m3 is
+signed. With ``amax = max|x|`` over the row, ``scale_h`` is the smallest fp16
+``>= amax / 448`` (round up: ``h = fp16_rne(v)``, and the next fp16 up if
+``float(h) < v``), so ``|x| / scale_h <= 448`` and nothing saturates;
+``amax == 0`` gives ``scale_h = 0`` and all codes 0. ``code =
+e4m3fn_rne(clamp(x / scale, -448, 448))`` with ``scale = float(scale_h)``,
+the stored value; the NaN codes 0x7f / 0xff are never produced. ``w =
+decode(code) * scale`` in fp32. Inputs are assumed finite with ``amax <=
+448 * 65504`` (the scale must fit fp16). The error is relative, at most 2^-4
+of each element (2^-10 * scale in e4m3's subnormal range), where INT8's is
+absolute.
 """
 
 from __future__ import annotations
@@ -34,16 +49,26 @@ from torchrec_amd.modules.embedding_modules import (
 )
 from torchrec_amd.sparse.jagged_tensor import JaggedTensor, KeyedJaggedTensor, KeyedTensor
 
-_QUANT_DATA_TYPES = (DataType.INT8, DataType.INT4, DataType.INT2)
-# output columns one lane of the n-bit kernels owns, by width (quant_tbe.hip: CodeUnit)
-_LANE_COLS = {8: 4, 4: 8, 2: 8}
+_QUANT_DATA_TYPES = (DataType.INT8, DataType.INT4, DataType.INT2, DataType.FP8)
+# Per-table format code, the values of the ``weight_bits`` tensor handed to the
+# n-bit ops: 8 / 4 / 2 are the integer widths; FP8 rows are 8 bits wide too, so
+# they carry a code of their own whose low byte is still the width
+# (quant_tbe.hip: kFormatFp8).
+FP8_FORMAT_CODE = 0x108
+# output columns one lane of the n-bit kernels owns, by format code (quant_tbe.hip: CodeUnit)
+_LANE_COLS = {8: 4, 4: 8, 2: 8, FP8_FORMAT_CODE: 4}
 # output_dtype -> the ops' code (the training TBE's: ops/tbe.py)
 _OUT_DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+_FP8_MAX = 448.0  # largest finite e4m3fn
+
+
+def _format_code(data_type: DataType) -> int:
+    return FP8_FORMAT_CODE if data_type is DataType.FP8 else DATA_TYPE_NUM_BITS[data_type]
 
 
 def quant_data_type(data_type: object) -> DataType:
-    """The quantized width a table is served at: INT8/INT4/INT2 (given as a
-    DataType or its name) are honoured, anything else means INT8."""
+    """The quantized format a table is served at: INT8/INT4/INT2/FP8 (given as
+    a DataType or its name) are honoured, anything else means INT8."""
     for dt in _QUANT_DATA_TYPES:
         if data_type is dt or data_type == dt.name:
             return dt
@@ -55,6 +80,14 @@ def int8_row_stride(D: int) -> int:
 
 
 def _check_nbit_dim(D: int, bits: int) -> None:
+    """``bits`` is a format code: 8, 4, 2 or FP8_FORMAT_CODE."""
+    if bits == FP8_FORMAT_CODE:
+        if D <= 0 or D % 4 != 0:
+            raise ValueError(
+                f"embedding_dim {D} cannot be packed as FP8: D must be a multiple of 4 "
+                f"(a row is a whole number of 32-bit code words)"
+            )
+        return
     if bits not in (8, 4, 2):
         raise ValueError(f"quantized rows are 8, 4 or 2 bits wide, got {bits}")
     if D <= 0 or (D * bits) % 32 != 0:
@@ -155,11 +188,53 @@ def dequantize_rowwise_nbit(packed: torch.Tensor, D: int, bits: int) -> torch.Te
     return q * scale.unsqueeze(1) + bias.unsqueeze(1)
 
 
+def fp8_row_stride(D: int) -> int:
+    """Bytes per packed FP8 row: D codes + fp16 scale + 2 reserved bytes,
+    rounded up to 16 (the INT8 stride)."""
+    _check_nbit_dim(D, FP8_FORMAT_CODE)
+    return int8_row_stride(D)
+
+
+def _fp16_round_up(v: torch.Tensor) -> torch.Tensor:
+    """Smallest fp16 >= v for finite fp32 v >= 0: round to nearest, then step
+    up once where that fell short (the HIP kernel does the same)."""
+    h = v.half()
+    short = h.float() < v
+    return (h.view(torch.int16) + short.to(torch.int16)).view(torch.float16)
+
+
+def quantize_rowwise_fp8(weights: torch.Tensor) -> torch.Tensor:
+    """fp32 [R, D] -> packed FP8 rows [R, stride] (CPU ref / HIP kernel); the
+    format and its assumptions are in the module docstring."""
+    R, D = weights.shape
+    stride = fp8_row_stride(D)
+    if weights.is_cuda:
+        ops.hip_ops()
+        return torch.ops.trec_amd.quantize_rowwise_fp8(weights)
+    w = weights.float()
+    scale_h = _fp16_round_up(w.abs().amax(dim=1) / _FP8_MAX)
+    scale = scale_h.float().unsqueeze(1)
+    r = (w / scale).clamp(-_FP8_MAX, _FP8_MAX)
+    r = torch.where(scale == 0, torch.zeros_like(r), r)
+    out = torch.zeros(R, stride, dtype=torch.uint8)
+    out[:, :D] = r.to(torch.float8_e4m3fn).view(torch.uint8)
+    out[:, D : D + 2] = scale_h.view(torch.uint8).reshape(R, 2)
+    return out
+
+
+def dequantize_rowwise_fp8(packed: torch.Tensor, D: int) -> torch.Tensor:
+    """Packed FP8 rows -> fp32 [R, D]: decode(code) * the stored fp16 scale."""
+    R = packed.shape[0]
+    codes = packed[:, :D].contiguous().view(torch.float8_e4m3fn).float()
+    scale = packed[:, D : D + 2].contiguous().view(torch.float16).float()
+    return codes * scale.reshape(R, 1)
+
+
 class QuantTableBatchedEmbeddingBags(nn.Module):
     """Inference-only quantized TBE (pooled). Flat packed buffer, per-table byte
-    offsets and per-table width (``weight_dtypes``: INT8/INT4/INT2, None = all
-    INT8). GPU path = tbe_forward_pooled_int8 when every table is INT8, else
-    tbe_forward_pooled_nbit (one launch for mixed widths); CPU path = dequant
+    offsets and per-table format (``weight_dtypes``: INT8/INT4/INT2/FP8, None =
+    all INT8). GPU path = tbe_forward_pooled_int8 when every table is INT8, else
+    tbe_forward_pooled_nbit (one launch for mixed formats); CPU path = dequant
     reference. ``output_dtype`` (fp32 / bf16 / fp16) is the dtype of every
     lookup's result: the arithmetic is fp32 and the value is rounded once."""
 
@@ -192,12 +267,14 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
             raise ValueError(f"weight_dtypes has {len(weight_dtypes)} entries for {T} tables")
         for dt in weight_dtypes:
             if dt not in _QUANT_DATA_TYPES:
-                raise ValueError(f"quantized tables are INT8, INT4 or INT2, got {dt}")
+                raise ValueError(f"quantized tables are INT8, INT4, INT2 or FP8, got {dt}")
         self._weight_dtypes = list(weight_dtypes)
         self._bits = [DATA_TYPE_NUM_BITS[dt] for dt in weight_dtypes]
-        self._all_int8 = all(b == 8 for b in self._bits)
+        # what the n-bit ops switch on: the width, or FP8_FORMAT_CODE
+        self._formats = [_format_code(dt) for dt in weight_dtypes]
+        self._all_int8 = all(dt is DataType.INT8 for dt in weight_dtypes)
         if not self._all_int8:
-            for (name, _, dim), b in zip(specs, self._bits):
+            for (name, _, dim), b in zip(specs, self._formats):
                 try:
                     _check_nbit_dim(dim, b)
                 except ValueError as e:
@@ -207,7 +284,7 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         self._num_features = F
         self.pooling = pooling
         byte_offsets = [0]
-        for (_, rows, dim), b in zip(specs, self._bits):
+        for (_, rows, dim), b in zip(specs, self._formats):
             byte_offsets.append(byte_offsets[-1] + rows * self._stride(dim, b))
         dims = [s[2] for s in specs]
         feat_dims = [dims[t] for t in self._feature_table_map]
@@ -217,9 +294,9 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         self._total_D = d_out[-1]
         self._max_D = max(dims) if dims else 0
         # widest row in lane units, what the n-bit launch is sized by: a lane
-        # owns 4 columns of an INT8 row and 8 of an INT4 or INT2 row
+        # owns 4 columns of an INT8 or FP8 row and 8 of an INT4 or INT2 row
         self._max_units = max(
-            (d // _LANE_COLS[b] for d, b in zip(dims, self._bits)), default=0
+            (d // _LANE_COLS[b] for d, b in zip(dims, self._formats)), default=0
         )
         qw = torch.zeros(byte_offsets[-1], dtype=torch.uint8, device=qdevice)
         if getattr(self, "_uvm", False):
@@ -228,21 +305,25 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         reg = lambda n, t: self.register_buffer(n, t.to(device), persistent=False)
         reg("_table_byte_offsets", torch.tensor(byte_offsets[:-1], dtype=torch.int64))
         reg("_dims_t", torch.tensor(dims, dtype=torch.int32))
-        reg("_weight_bits_t", torch.tensor(self._bits, dtype=torch.int32))
+        reg("_weight_bits_t", torch.tensor(self._formats, dtype=torch.int32))
         reg("_feat_table_t", torch.tensor(self._feature_table_map, dtype=torch.int32))
         reg("_d_out_offsets", torch.tensor(d_out, dtype=torch.int64))
         reg("_empty_f", torch.empty(0, dtype=torch.float32))
 
     @staticmethod
     def _stride(dim: int, bits: int) -> int:
-        # INT8 keeps its own stride rule (no dim check: CPU lookups of odd
-        # dims keep working as before)
+        # ``bits`` is a format code. INT8 keeps its own stride rule (no dim
+        # check: CPU lookups of odd dims keep working as before)
+        if bits == FP8_FORMAT_CODE:
+            return fp8_row_stride(dim)
         return int8_row_stride(dim) if bits == 8 else nbit_row_stride(dim, bits)
 
     def load_float_table(self, i: int, weights: torch.Tensor) -> None:
         name, rows, dim = self._specs[i]
         w = weights.to(self.qweights.device).float()
-        if self._bits[i] == 8:
+        if self._formats[i] == FP8_FORMAT_CODE:
+            packed = quantize_rowwise_fp8(w)
+        elif self._bits[i] == 8:
             packed = quantize_rowwise_int8(w)
         else:
             packed = quantize_rowwise_nbit(w, self._bits[i])
@@ -252,12 +333,14 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
     def packed_table(self, i: int) -> torch.Tensor:
         name, rows, dim = self._specs[i]
         start = int(self._table_byte_offsets[i])
-        stride = self._stride(dim, self._bits[i])
+        stride = self._stride(dim, self._formats[i])
         return self.qweights[start : start + rows * stride].view(rows, stride)
 
     def dequantized_table(self, i: int) -> torch.Tensor:
         """fp32 [rows, dim] of table ``i`` from its packed bytes."""
         name, rows, dim = self._specs[i]
+        if self._formats[i] == FP8_FORMAT_CODE:
+            return dequantize_rowwise_fp8(self.packed_table(i), dim)
         if self._bits[i] == 8:
             return dequantize_rowwise_int8(self.packed_table(i), dim)
         return dequantize_rowwise_nbit(self.packed_table(i), dim, self._bits[i])
@@ -381,13 +464,15 @@ def _resolve_weight_dtype(
 ) -> DataType:
     dt = (per_table_weight_dtype or {}).get(name, weight_dtype)
     if dt not in _QUANT_DATA_TYPES:
-        raise ValueError(f"table {name}: quantized tables are INT8, INT4 or INT2, got {dt}")
+        raise ValueError(
+            f"table {name}: quantized tables are INT8, INT4, INT2 or FP8, got {dt}"
+        )
     return dt
 
 
 class EmbeddingBagCollection(nn.Module):
     """Quantized EBC (reference quant/embedding_modules.py:346). Each table is
-    served at its config's ``data_type`` when that is INT8/INT4/INT2, else INT8."""
+    served at its config's ``data_type`` when that is INT8/INT4/INT2/FP8, else INT8."""
 
     def __init__(
         self,
@@ -472,8 +557,8 @@ class EmbeddingBagCollection(nn.Module):
 
 class EmbeddingCollection(nn.Module):
     """Quantized sequence EC (reference quant/embedding_modules.py:748). Each
-    table is served at its config's ``data_type`` when that is INT8/INT4/INT2,
-    else INT8."""
+    table is served at its config's ``data_type`` when that is
+    INT8/INT4/INT2/FP8, else INT8."""
 
     def __init__(
         self,
