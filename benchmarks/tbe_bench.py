@@ -4,6 +4,7 @@ torchrec/distributed/benchmark/ + FBGEMM TBE device benchmarks).
 Run on an MI355X:
     python benchmarks/tbe_bench.py            # all suites
     python benchmarks/tbe_bench.py --suite tbe
+    python benchmarks/tbe_bench.py --update-rows   # in-place row update vs table reload
 Prints one JSON line per measurement.
 """
 
@@ -29,6 +30,24 @@ def _time_kernel(fn, iters=50, warmup=10) -> float:
         fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / iters * 1e6  # us
+
+
+def _time_graph(fn, calls=50, replays=400) -> float:
+    """Device time of one ``fn()``: ``calls`` of them captured in one graph,
+    so the host's enqueue cost is paid once per replay, not per call."""
+    fn()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(calls):
+            fn()
+    graph.replay()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(replays):
+        graph.replay()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / (replays * calls) * 1e6  # us
 
 
 def bench_tbe(B=8192, D=128, tables=26, rows=1_000_000, L=1, precision="fp32",
@@ -268,13 +287,61 @@ def bench_quant_fp8_suite(B=8192, D=128, tables=26):
         }))
 
 
+def bench_update_rows(N=4096, D=128, rows=100_000):
+    """In-place update of N rows of one served table (``update_rows``, one
+    kernel) per format, against the only alternative without it:
+    ``load_float_table`` of the whole [rows, D] fp32 table (quantise into a
+    second packed copy, then copy that over the served one). ``update_rows_us``
+    is the eager call, host enqueue included; ``update_rows_graph_us`` is the
+    device time of one update (50 of them replayed from a graph)."""
+    from torchrec_amd.modules.embedding_configs import DataType
+    from torchrec_amd.quant.embedding_modules import QuantTableBatchedEmbeddingBags
+
+    torch.manual_seed(0)
+    full = torch.randn(rows, D, device="cuda")
+    ids = torch.randperm(rows, device="cuda")[:N].contiguous()
+    new = torch.randn(N, D, device="cuda")
+    for dt in (DataType.INT8, DataType.INT4, DataType.INT2, DataType.FP8):
+        q = QuantTableBatchedEmbeddingBags(
+            [("t0", rows, D)], device=torch.device("cuda"), weight_dtypes=[dt]
+        )
+        q.load_float_table(0, full)
+        # three timings each, alternating; windows of a few tenths of a second
+        upd, reload_us = [], []
+        for _ in range(3):
+            upd.append(
+                _time_kernel(lambda: q.update_rows({0: (ids, new)}), iters=20000, warmup=20)
+            )
+            reload_us.append(
+                _time_kernel(lambda: q.load_float_table(0, full), iters=1000, warmup=5)
+            )
+        in_graph = [_time_graph(lambda: q.update_rows({0: (ids, new)})) for _ in range(3)]
+        applied = int(q.update_rows({0: (ids, new)})[0])
+        print(json.dumps({
+            "bench": "quant_tbe_update_rows", "weight_dtype": dt.name, "N": N, "D": D,
+            "table_rows": rows, "applied": applied,
+            "update_rows_us": round(sorted(upd)[1], 1),
+            "update_rows_us_runs": [round(t, 1) for t in upd],
+            "update_rows_graph_us": round(sorted(in_graph)[1], 2),
+            "update_rows_graph_us_runs": [round(t, 2) for t in in_graph],
+            "load_float_table_us": round(sorted(reload_us)[1], 1),
+            "load_float_table_us_runs": [round(t, 1) for t in reload_us],
+            "fp32_bytes_in": N * D * 4, "full_table_fp32_bytes": rows * D * 4,
+        }))
+
+
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
+    p.add_argument("--update-rows", action="store_true",
+                   help="time the in-place row update against a whole-table reload, then exit")
     p.add_argument("--suite", default="all",
                    choices=["all", "tbe", "tbe_sweep", "interaction", "sort",
                             "col_sum", "quant", "quant_out", "quant_fp8"])
     a = p.parse_args()
     assert torch.cuda.is_available(), "run on a GPU box"
+    if a.update_rows:
+        bench_update_rows()
+        sys.exit(0)
     if a.suite in ("all", "tbe"):
         bench_tbe()
         bench_tbe(precision="bf16")

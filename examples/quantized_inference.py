@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch
 
-from torchrec_amd.inference.modules import quantize_inference_model
+from torchrec_amd.inference.modules import apply_model_delta, quantize_inference_model
 from torchrec_amd.models.dlrm import DLRM
 from torchrec_amd.modules.embedding_configs import DataType, EmbeddingBagConfig
 from torchrec_amd.modules.embedding_modules import EmbeddingBagCollection
@@ -59,6 +59,17 @@ def main() -> None:
     with torch.no_grad():
         logits = qmodel(dense, kjt)
     print("predictions:", torch.sigmoid(logits.squeeze(-1)).cpu().tolist())
+
+    # publish a training delta: fresh float rows for a few ids of table t0 (what
+    # ModelDeltaTracker.get_unique() returns in UpdateMode.LAST) requantise in
+    # place; nothing else in the served tables moves
+    ids = values[:B].unique()
+    delta = {"t0": (ids, torch.randn(ids.numel(), 16, device=device))}
+    applied = apply_model_delta(qmodel, delta)
+    with torch.no_grad():
+        logits = qmodel(dense, kjt)
+    print("rows updated:", {n: int(c) for n, c in applied.items()})
+    print("predictions after the delta:", torch.sigmoid(logits.squeeze(-1)).cpu().tolist())
 
 
 if __name__ == "__main__":

@@ -14,7 +14,10 @@ import torch.nn as nn
 
 from torchrec_amd.distributed.embedding import ShardedEmbeddingCollection
 from torchrec_amd.distributed.embedding_sharding import ShardedTableLocal
-from torchrec_amd.distributed.quant_embeddingbag import with_module_output_dtype
+from torchrec_amd.distributed.quant_embeddingbag import (
+    apply_delta_to_shards,
+    with_module_output_dtype,
+)
 from torchrec_amd.distributed.types import (
     EmbeddingModuleShardingPlan,
     ModuleSharder,
@@ -24,6 +27,7 @@ from torchrec_amd.distributed.types import (
 from torchrec_amd.quant.embedding_modules import (
     EmbeddingCollection as QuantEmbeddingCollection,
     QuantTableBatchedEmbeddingBags,
+    check_delta_tables,
     quant_data_type,
 )
 
@@ -89,6 +93,10 @@ class ShardedQuantEmbeddingCollection(ShardedEmbeddingCollection):
         W = env.world_size
         for lookup in self._lookups:
             qtbe = lookup._qtbe
+            # each table's global row range on this rank, from its REAL local
+            # row count: a rank that owns no row of a table serves a one-row
+            # placeholder, which an update must not touch
+            lookup._row_windows = []
             for ti, (name, local_rows, dim) in enumerate(qtbe._specs):
                 si = by_name[name]
                 packed = src.packed_table(si)
@@ -102,6 +110,22 @@ class ShardedQuantEmbeddingCollection(ShardedEmbeddingCollection):
                 shard = packed[lo : lo + local_rows]
                 dst = qtbe.packed_table(ti)
                 dst[: shard.shape[0]].copy_(shard.to(dst.device))
+                lookup._row_windows.append((lo, lo + lookup._real_rows[ti]))
+        self._quant_table_names = [s[0] for s in src._specs]
+
+    def update_embeddings(self, delta: Dict[str, Any]) -> Dict[str, torch.Tensor]:
+        """Apply a model delta (table name -> ``UniqueRows`` or ``(ids, rows)``,
+        GLOBAL ids) to this rank's shards; every rank passes the same delta.
+        The window of a local table is the shard's own global row range (TW:
+        ``[0, rows)`` on the owner; RW: ``[lo, lo + local_rows)`` with ``lo =
+        rank * ceil(rows / W)``), the rest is dropped on the device: no
+        collective. Returns table name -> entries applied on THIS rank."""
+        check_delta_tables(delta, self._quant_table_names, "this sharded quant EC")
+        return apply_delta_to_shards(
+            ((lookup._qtbe, lookup._row_windows) for lookup in self._lookups),
+            delta,
+            self._device,
+        )
 
     def _make_lookup(
         self, tables: List[ShardedTableLocal], D: int, dense: bool = False
@@ -113,7 +137,9 @@ class ShardedQuantEmbeddingCollection(ShardedEmbeddingCollection):
             weight_dtypes=[quant_data_type(t.data_type) for t in tables],
             output_dtype=self._quant_out_dtype_pre,
         )
-        return _QuantSeqLookup(qtbe, D)
+        lookup = _QuantSeqLookup(qtbe, D)
+        lookup._real_rows = [t.local_rows for t in tables]
+        return lookup
 
     def forward(self, features):
         with torch.no_grad():

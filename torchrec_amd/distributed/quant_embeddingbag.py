@@ -9,7 +9,7 @@ table's own format (INT8/INT4/INT2/FP8).
 
 from __future__ import annotations
 
-from typing import Any, Dict, Optional, Type
+from typing import Any, Dict, Iterable, List, Optional, Tuple, Type
 
 import torch
 
@@ -25,7 +25,10 @@ from torchrec_amd.distributed.types import (
 )
 from torchrec_amd.quant.embedding_modules import (
     EmbeddingBagCollection as QuantEmbeddingBagCollection,
+    QuantTableBatchedEmbeddingBags,
+    check_delta_tables,
     int8_row_stride,
+    update_tbe_from_delta,
 )
 
 
@@ -41,6 +44,21 @@ def with_module_output_dtype(
     if "output_dtype" not in fused_params:
         fused_params["output_dtype"] = _OUT_DTYPE_NAME[module.output_dtype()]
     return fused_params
+
+
+def apply_delta_to_shards(
+    shards: Iterable[Tuple[QuantTableBatchedEmbeddingBags, List[Tuple[int, int]]]],
+    delta: Dict[str, Any],
+    device: torch.device,
+) -> Dict[str, torch.Tensor]:
+    """``update_rows`` on each local quant TBE with its tables' global row
+    windows; table name -> entries applied on this rank, for every table of
+    ``delta`` (0 for one this rank holds no rows of)."""
+    applied = {name: torch.zeros((), dtype=torch.int64, device=device) for name in delta}
+    for qtbe, windows in shards:
+        for name, n in update_tbe_from_delta(qtbe, delta, windows).items():
+            applied[name] = applied[name] + n.to(device)
+    return applied
 
 
 class ShardedQuantEmbeddingBagCollection(ShardedEmbeddingBagCollection):
@@ -67,6 +85,27 @@ class ShardedQuantEmbeddingBagCollection(ShardedEmbeddingBagCollection):
                     shard = packed[t.row_offset : t.row_offset + t.local_rows]
                     dst = qtbe.packed_table(ti)
                     dst.copy_(shard.to(dst.device))
+        self._quant_table_names = [s[0] for s in src._specs]
+
+    def update_embeddings(self, delta: Dict[str, Any]) -> Dict[str, torch.Tensor]:
+        """Apply a model delta (table name -> ``UniqueRows`` or ``(ids, rows)``,
+        GLOBAL ids) to this rank's shards. Every rank passes the same delta:
+        each local quant TBE takes its shard's own global row range as the
+        window (TW: ``[0, rows)`` on the owner, the other ranks do not hold the
+        table; RW: ``[row_offset, row_offset + local_rows)``) and drops the
+        rest on the device, so there is no collective and no host-side
+        filtering. Returns table name -> entries applied on THIS rank (0 where
+        the rows live elsewhere)."""
+        check_delta_tables(delta, self._quant_table_names, "this sharded quant EBC")
+        return apply_delta_to_shards(
+            (
+                (qtbe, [(t.row_offset, t.row_offset + t.local_rows) for t in group])
+                for lookup in self._lookups
+                for group, qtbe in zip(lookup._grouped_tables, lookup._emb_modules)
+            ),
+            delta,
+            self._device,
+        )
 
     def forward(self, features):  # inference: no autograd
         with torch.no_grad():

@@ -61,6 +61,50 @@ def quantize_inference_model(
     return model
 
 
+def apply_model_delta(model: nn.Module, delta: Dict[str, Any]) -> Dict[str, torch.Tensor]:
+    """Publish a training delta into a served model, in place.
+
+    ``delta`` maps a table name to the model tracker's ``UniqueRows`` (
+    ``ModelDeltaTracker.get_unique`` in ``UpdateMode.FIRST`` / ``LAST``) or to
+    ``(ids, rows)`` with global row ids. Every quant EBC / EC in ``model``,
+    sharded or not, requantises the rows of the tables it serves
+    (``update_embeddings``); on a sharded model every rank passes the same
+    delta and keeps its own rows. Returns table name -> entries applied on
+    this rank (0 is fine: the rows may live on another rank). A table of
+    ``delta`` that no module serves is an error, raised before anything is
+    written. Lookups on other streams are not ordered against the update (see
+    ``QuantTableBatchedEmbeddingBags.update_rows``)."""
+    targets = []
+    served: set = set()
+    for m in model.modules():
+        if not callable(getattr(m, "update_embeddings", None)):
+            continue
+        if isinstance(m, QuantEBC):
+            names = [t.name for t in m.embedding_bag_configs()]
+        elif isinstance(m, QuantEC):
+            names = [t.name for t in m.embedding_configs()]
+        else:
+            names = getattr(m, "_quant_table_names", None)
+            if names is None:
+                continue
+        targets.append((m, names))
+        served.update(names)
+    missing = [n for n in delta if n not in served]
+    if missing:
+        raise KeyError(
+            f"apply_model_delta: no quantized module of the model serves {missing} "
+            f"(served: {sorted(served)})"
+        )
+    applied: Dict[str, torch.Tensor] = {}
+    for m, names in targets:
+        part = {n: delta[n] for n in names if n in delta}
+        if not part:
+            continue
+        for n, c in m.update_embeddings(part).items():
+            applied[n] = applied[n] + c.to(applied[n].device) if n in applied else c
+    return applied
+
+
 def shard_quant_model(
     model: nn.Module,
     world_size: int = 1,

@@ -138,6 +138,11 @@ at::Tensor tbe_forward_seq_nbit(const at::Tensor& qweights,
                                 const at::Tensor& weight_bits, const at::Tensor& feat_table,
                                 const at::Tensor& feat_val_offsets, const at::Tensor& indices,
                                 int64_t D_out, int64_t max_units, int64_t output_dtype);
+at::Tensor quant_tbe_update_rows(at::Tensor qweights, const at::Tensor& table_byte_offsets,
+                                 const at::Tensor& dims, const at::Tensor& weight_bits,
+                                 const at::Tensor& row_lo, const at::Tensor& row_hi,
+                                 const at::Tensor& upd_offsets, const at::Tensor& upd_rows,
+                                 const at::Tensor& values, const at::Tensor& val_offsets);
 
 // interaction.hip
 at::Tensor col_sum(const at::Tensor& input);
@@ -281,6 +286,10 @@ TORCH_LIBRARY(trec_amd, m) {
       "tbe_forward_seq_nbit(Tensor qweights, Tensor table_byte_offsets, Tensor dims,"
       " Tensor weight_bits, Tensor feat_table, Tensor feat_val_offsets, Tensor indices,"
       " int D_out, int max_units, int output_dtype=0) -> Tensor");
+  m.def(
+      "quant_tbe_update_rows(Tensor(a!) qweights, Tensor table_byte_offsets, Tensor dims,"
+      " Tensor weight_bits, Tensor row_lo, Tensor row_hi, Tensor upd_offsets, Tensor upd_rows,"
+      " Tensor values, Tensor val_offsets) -> Tensor");
   m.def("col_sum(Tensor input) -> Tensor");
   m.def("interaction_forward(Tensor dense, Tensor sparse, Tensor pi, Tensor pj) -> Tensor");
   m.def("relu_bwd_col_sum(Tensor grad_out, Tensor y) -> (Tensor, Tensor)");
@@ -336,6 +345,7 @@ TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
   m.impl("quantize_rowwise_fp8", trec_amd::quantize_rowwise_fp8);
   m.impl("tbe_forward_pooled_nbit", trec_amd::tbe_forward_pooled_nbit);
   m.impl("tbe_forward_seq_nbit", trec_amd::tbe_forward_seq_nbit);
+  m.impl("quant_tbe_update_rows", trec_amd::quant_tbe_update_rows);
   m.impl("col_sum", trec_amd::col_sum);
   m.impl("interaction_forward", trec_amd::interaction_forward);
   m.impl("relu_bwd_col_sum", trec_amd::relu_bwd_col_sum);

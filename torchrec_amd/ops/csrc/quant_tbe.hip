@@ -55,38 +55,41 @@ __host__ __device__ inline int64_t int8_row_stride(int D) {
 // fp32 [R, D] -> int8 rowwise quantized [R, row_stride] bytes
 // ---------------------------------------------------------------------------
 
+// one wave quantises one row; lane l of the wave. Shared by the whole-table
+// kernel and quant_tbe_update_rows_kernel. Writes [0, D + 4) of orow only.
+__device__ __forceinline__ void quantize_row_int8(const float* __restrict__ row, int D,
+                                                  uint8_t* __restrict__ orow, int l) {
+  float mn = INFINITY, mx = -INFINITY;
+  for (int d = l; d < D; d += kWaveSize) {
+    float v = row[d];
+    mn = fminf(mn, v);
+    mx = fmaxf(mx, v);
+  }
+#pragma unroll
+  for (int off = kWaveSize / 2; off > 0; off >>= 1) {
+    mn = fminf(mn, __shfl_xor(mn, off, kWaveSize));
+    mx = fmaxf(mx, __shfl_xor(mx, off, kWaveSize));
+  }
+  float scale = (mx - mn) / 255.f;
+  float inv = scale > 0.f ? 1.f / scale : 0.f;
+  for (int d = l; d < D; d += kWaveSize) {
+    float q = (row[d] - mn) * inv;
+    orow[d] = static_cast<uint8_t>(fminf(fmaxf(q + 0.5f, 0.f), 255.f));
+  }
+  if (l == 0) {
+    __half* sb = reinterpret_cast<__half*>(orow + D);
+    sb[0] = __float2half(scale);
+    sb[1] = __float2half(mn);
+  }
+}
+
 __global__ void quantize_rowwise_int8_kernel(const float* __restrict__ w, int64_t R, int D,
                                              int64_t stride, uint8_t* __restrict__ out) {
   // one wave per row
   int64_t wave = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWaveSize;
   int64_t n_waves = (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWaveSize;
   int l = lane_id();
-  for (int64_t r = wave; r < R; r += n_waves) {
-    const float* row = w + r * D;
-    float mn = INFINITY, mx = -INFINITY;
-    for (int d = l; d < D; d += kWaveSize) {
-      float v = row[d];
-      mn = fminf(mn, v);
-      mx = fmaxf(mx, v);
-    }
-#pragma unroll
-    for (int off = kWaveSize / 2; off > 0; off >>= 1) {
-      mn = fminf(mn, __shfl_xor(mn, off, kWaveSize));
-      mx = fmaxf(mx, __shfl_xor(mx, off, kWaveSize));
-    }
-    float scale = (mx - mn) / 255.f;
-    float inv = scale > 0.f ? 1.f / scale : 0.f;
-    uint8_t* orow = out + r * stride;
-    for (int d = l; d < D; d += kWaveSize) {
-      float q = (row[d] - mn) * inv;
-      orow[d] = static_cast<uint8_t>(fminf(fmaxf(q + 0.5f, 0.f), 255.f));
-    }
-    if (l == 0) {
-      __half* sb = reinterpret_cast<__half*>(orow + D);
-      sb[0] = __float2half(scale);
-      sb[1] = __float2half(mn);
-    }
-  }
+  for (int64_t r = wave; r < R; r += n_waves) quantize_row_int8(w + r * D, D, out + r * stride, l);
 }
 
 at::Tensor quantize_rowwise_int8(const at::Tensor& weights) {
@@ -307,7 +310,9 @@ __host__ __device__ inline int64_t nbit_row_stride(int code_bytes) {
   return ((code_bytes + 4 /*scale+bias*/ + 15) / 16) * 16;
 }
 
-template <int BITS>
+// ZERO_PAD: the whole-table quantiser also zeroes the row's padding; the
+// in-place row update leaves every byte past code_bytes + 4 as it is.
+template <int BITS, bool ZERO_PAD = true>
 __device__ __forceinline__ void quantize_row_nbit(const float* __restrict__ row, int D,
                                                   uint8_t* __restrict__ orow, int64_t stride,
                                                   int l) {
@@ -350,8 +355,10 @@ __device__ __forceinline__ void quantize_row_nbit(const float* __restrict__ row,
     sb[1] = bias_h;
   }
   // padding is part of the packed buffer (state dicts, RW row slices): zero it
-  int n_pad = static_cast<int>(stride / 4) - n_words - 1;
-  for (int k = l; k < n_pad; k += kWaveSize) owords[n_words + 1 + k] = 0u;
+  if constexpr (ZERO_PAD) {
+    int n_pad = static_cast<int>(stride / 4) - n_words - 1;
+    for (int k = l; k < n_pad; k += kWaveSize) owords[n_words + 1 + k] = 0u;
+  }
 }
 
 template <int BITS>
@@ -406,42 +413,50 @@ __device__ __forceinline__ float fp8_prescale(float x, float scale) {
   return fminf(fmaxf(x / scale, -448.f), 448.f);
 }
 
+// one wave quantises one row (ZERO_PAD as in quantize_row_nbit)
+template <bool ZERO_PAD = true>
+__device__ __forceinline__ void quantize_row_fp8(const float* __restrict__ row, int D,
+                                                 uint8_t* __restrict__ orow, int64_t stride,
+                                                 int l) {
+  int n_words = D / 4;
+  float amax = 0.f;
+  for (int d = l; d < D; d += kWaveSize) amax = fmaxf(amax, fabsf(row[d]));
+#pragma unroll
+  for (int off = kWaveSize / 2; off > 0; off >>= 1)
+    amax = fmaxf(amax, __shfl_xor(amax, off, kWaveSize));
+  __half scale_h = half_round_up(amax / 448.f);
+  // codes are taken against the STORED scale
+  float scale = __half2float(scale_h);
+  uint32_t* owords = reinterpret_cast<uint32_t*>(orow);
+  for (int wi = l; wi < n_words; wi += kWaveSize) {
+    int word = 0;
+    if (scale != 0.f) {
+      const float* x = row + wi * 4;
+      // packed convert: two floats -> two e4m3fn bytes (round to nearest
+      // even) into the low / high half of the word
+      word = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_prescale(x[0], scale),
+                                             fp8_prescale(x[1], scale), word, false);
+      word = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_prescale(x[2], scale),
+                                             fp8_prescale(x[3], scale), word, true);
+    }
+    owords[wi] = static_cast<uint32_t>(word);
+  }
+  // scale + the two reserved zero bytes are one word
+  if (l == 0) owords[n_words] = static_cast<uint32_t>(__half_as_ushort(scale_h));
+  if constexpr (ZERO_PAD) {
+    int n_pad = static_cast<int>(stride / 4) - n_words - 1;
+    for (int k = l; k < n_pad; k += kWaveSize) owords[n_words + 1 + k] = 0u;
+  }
+}
+
 __global__ void quantize_rowwise_fp8_kernel(const float* __restrict__ w, int64_t R, int D,
                                             int64_t stride, uint8_t* __restrict__ out) {
   // one wave per row
   int64_t wave = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWaveSize;
   int64_t n_waves = (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWaveSize;
   int l = lane_id();
-  int n_words = D / 4;
-  for (int64_t r = wave; r < R; r += n_waves) {
-    const float* row = w + r * D;
-    float amax = 0.f;
-    for (int d = l; d < D; d += kWaveSize) amax = fmaxf(amax, fabsf(row[d]));
-#pragma unroll
-    for (int off = kWaveSize / 2; off > 0; off >>= 1)
-      amax = fmaxf(amax, __shfl_xor(amax, off, kWaveSize));
-    __half scale_h = half_round_up(amax / 448.f);
-    // codes are taken against the STORED scale
-    float scale = __half2float(scale_h);
-    uint32_t* owords = reinterpret_cast<uint32_t*>(out + r * stride);
-    for (int wi = l; wi < n_words; wi += kWaveSize) {
-      int word = 0;
-      if (scale != 0.f) {
-        const float* x = row + wi * 4;
-        // packed convert: two floats -> two e4m3fn bytes (round to nearest
-        // even) into the low / high half of the word
-        word = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_prescale(x[0], scale),
-                                               fp8_prescale(x[1], scale), word, false);
-        word = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_prescale(x[2], scale),
-                                               fp8_prescale(x[3], scale), word, true);
-      }
-      owords[wi] = static_cast<uint32_t>(word);
-    }
-    // scale + the two reserved zero bytes are one word
-    if (l == 0) owords[n_words] = static_cast<uint32_t>(__half_as_ushort(scale_h));
-    int n_pad = static_cast<int>(stride / 4) - n_words - 1;
-    for (int k = l; k < n_pad; k += kWaveSize) owords[n_words + 1 + k] = 0u;
-  }
+  for (int64_t r = wave; r < R; r += n_waves)
+    quantize_row_fp8(w + r * D, D, out + r * stride, stride, l);
 }
 
 at::Tensor quantize_rowwise_fp8(const at::Tensor& weights) {
@@ -747,6 +762,152 @@ at::Tensor tbe_forward_seq_nbit(
 #undef TBE_NBS_LAUNCH_T
 #undef TBE_NBIT_DISPATCH
   return out;
+}
+
+// ===========================================================================
+// In-place row update of a served table from fp32 rows (online delta
+// publishing; reference IntNBitTableBatchedEmbeddingBags in-place update).
+//
+// Contract:
+//  * Entry n of table t's segment (upd_offsets[t] <= n < upd_offsets[t+1]) has
+//    the global row id r = upd_rows[n] and the fp32 row at values +
+//    val_offsets[t] + (n - upd_offsets[t]) * dims[t]. It is applied only if
+//    row_lo[t] <= r < row_hi[t], to local row r - row_lo[t]; every other entry
+//    is dropped here, on the device. [0, rows) bounds-checks an unsharded
+//    table; a shard's own global row range lets every rank take the same full
+//    delta and keep its rows. An entry whose local row would end past the
+//    table's bytes in qweights (a window wider than the table) is dropped too.
+//  * The first code_bytes + 4 bytes of an applied row are exactly what the
+//    table's own whole-table quantiser writes for that fp32 row: format 8 is
+//    quantize_row_int8 (NOT quantize_row_nbit<8>: the scale rounds
+//    differently), any D; 4 / 2 are quantize_row_nbit; kFormatFp8 is
+//    quantize_row_fp8.
+//  * No other byte of qweights changes: not the row's padding, not its
+//    neighbours, not another table.
+//  * Ids within one table's segment must be unique; duplicates with different
+//    values race.
+//  * Ordered against lookups on the same stream only: a lookup running on
+//    another stream may see codes and scale of different versions.
+//  * applied[t] counts table t's applied entries. No host sync, no device
+//    value read on the host: capturable in a graph.
+//
+// Lane mapping: one wave per entry (grid-stride over N), so the window test,
+// the table search and the format switch are wave-uniform; inside a row the
+// lanes stride over elements (INT8) or 32-bit code words (INT4/INT2/FP8) as
+// in the whole-table quantisers, whose __device__ bodies these are.
+//
+// Counting: atomics on one address serialise. One atomicAdd per applied entry
+// made the kernel 54 us at N = 4096, the same at every format (a whole-table
+// requantise of 100k rows is 46 us). So a wave takes kUpdateEntriesPerWave
+// entries, sums what it applied per table, the block's waves pool their sums
+// in LDS and one lane issues one vector atomicAdd per table and block.
+// ===========================================================================
+
+constexpr int kUpdateEntriesPerWave = 4;
+
+__global__ void __launch_bounds__(kBlockThreads) quant_tbe_update_rows_kernel(
+    uint8_t* __restrict__ qweights, int64_t qweights_bytes,
+    const int64_t* __restrict__ table_byte_offsets,  // [T]
+    const int32_t* __restrict__ dims,                // [T]
+    const int32_t* __restrict__ weight_bits,         // [T] 8 / 4 / 2 / kFormatFp8
+    const int64_t* __restrict__ row_lo,              // [T]
+    const int64_t* __restrict__ row_hi,              // [T]
+    const int64_t* __restrict__ upd_offsets,         // [T+1]
+    const int64_t* __restrict__ upd_rows,            // [N]
+    const float* __restrict__ values, const int64_t* __restrict__ val_offsets,  // [T]
+    int T, int64_t N, unsigned long long* __restrict__ applied) {
+  constexpr int kWaves = kBlockThreads / kWaveSize;
+  __shared__ int s_table[kWaves];
+  __shared__ unsigned long long s_count[kWaves];
+  int64_t wave = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWaveSize;
+  int64_t n_waves = (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWaveSize;
+  int l = lane_id();
+  // entries this wave applied to table pend_t and has not added to applied yet
+  int pend_t = 0;
+  unsigned long long pend = 0;
+  for (int64_t n = wave; n < N; n += n_waves) {
+    int t = upper_bound_segment(upd_offsets, T, n);
+    int64_t r = upd_rows[n];
+    int64_t lo = row_lo[t];
+    if (r < lo || r >= row_hi[t]) continue;
+    int bits = weight_bits[t];
+    int D = dims[t];
+    int64_t stride = bits == 8 ? int8_row_stride(D) : nbit_row_stride(D * (bits & 0xff) / 8);
+    int64_t row_byte = table_byte_offsets[t] + (r - lo) * stride;
+    int64_t table_end = t + 1 < T ? table_byte_offsets[t + 1] : qweights_bytes;
+    if (row_byte + stride > table_end) continue;
+    const float* src = values + val_offsets[t] + (n - upd_offsets[t]) * D;
+    uint8_t* dst = qweights + row_byte;
+    if (bits == 8) quantize_row_int8(src, D, dst, l);
+    else if (bits == 4) quantize_row_nbit<4, false>(src, D, dst, stride, l);
+    else if (bits == kFormatFp8) quantize_row_fp8<false>(src, D, dst, stride, l);
+    else quantize_row_nbit<2, false>(src, D, dst, stride, l);
+    if (t != pend_t) {
+      if (pend != 0 && l == 0) atomicAdd(applied + pend_t, pend);
+      pend_t = t;
+      pend = 0;
+    }
+    ++pend;
+  }
+  // every thread of the block gets here (the loop has no return): the waves
+  // pool what they still hold, and one lane adds it once per table
+  if (l == 0) {
+    s_table[wave_id()] = pend_t;
+    s_count[wave_id()] = pend;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 0; i < kWaves; ++i) {
+      unsigned long long c = s_count[i];
+      if (c == 0) continue;
+      for (int j = i + 1; j < kWaves; ++j)
+        if (s_table[j] == s_table[i]) {
+          c += s_count[j];
+          s_count[j] = 0;
+        }
+      atomicAdd(applied + s_table[i], c);
+    }
+  }
+}
+
+at::Tensor quant_tbe_update_rows(
+    at::Tensor qweights, const at::Tensor& table_byte_offsets, const at::Tensor& dims,
+    const at::Tensor& weight_bits, const at::Tensor& row_lo, const at::Tensor& row_hi,
+    const at::Tensor& upd_offsets, const at::Tensor& upd_rows, const at::Tensor& values,
+    const at::Tensor& val_offsets) {
+  TORCH_CHECK((qweights.is_cuda() || qweights.is_pinned()) &&
+                  qweights.scalar_type() == at::kByte && qweights.is_contiguous(),
+              "quant_tbe_update_rows: qweights must be contiguous uint8 on the device or pinned");
+  int64_t T = dims.numel();
+  auto is_i64 = [](const at::Tensor& t, int64_t n) {
+    return t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous() && t.numel() == n;
+  };
+  TORCH_CHECK(dims.is_cuda() && dims.scalar_type() == at::kInt && dims.is_contiguous(),
+              "quant_tbe_update_rows: dims must be int32 [T] on the device");
+  TORCH_CHECK(weight_bits.is_cuda() && weight_bits.scalar_type() == at::kInt &&
+                  weight_bits.is_contiguous() && weight_bits.numel() == T,
+              "quant_tbe_update_rows: weight_bits must be int32 [T] on the device");
+  TORCH_CHECK(is_i64(table_byte_offsets, T) && is_i64(row_lo, T) && is_i64(row_hi, T) &&
+                  is_i64(val_offsets, T) && is_i64(upd_offsets, T + 1),
+              "quant_tbe_update_rows: table_byte_offsets, row_lo, row_hi, val_offsets [T] and "
+              "upd_offsets [T+1] must be int64 on the device");
+  int64_t N = upd_rows.numel();
+  TORCH_CHECK(is_i64(upd_rows, N), "quant_tbe_update_rows: upd_rows must be int64 on the device");
+  TORCH_CHECK(values.is_cuda() && values.scalar_type() == at::kFloat && values.is_contiguous(),
+              "quant_tbe_update_rows: values must be contiguous fp32 on the device");
+  auto applied = at::zeros({T}, upd_rows.options());
+  if (N == 0 || T == 0) return applied;
+  int64_t n_waves = (N + kUpdateEntriesPerWave - 1) / kUpdateEntriesPerWave;
+  hipLaunchKernelGGL(quant_tbe_update_rows_kernel,
+                     dim3(grid_for(n_waves * kWaveSize, kBlockThreads)),
+                     dim3(kBlockThreads), 0, q_stream(), uvm_ptr<uint8_t>(qweights),
+                     qweights.numel(), table_byte_offsets.data_ptr<int64_t>(),
+                     dims.data_ptr<int32_t>(), weight_bits.data_ptr<int32_t>(),
+                     row_lo.data_ptr<int64_t>(), row_hi.data_ptr<int64_t>(),
+                     upd_offsets.data_ptr<int64_t>(), upd_rows.data_ptr<int64_t>(),
+                     values.data_ptr<float>(), val_offsets.data_ptr<int64_t>(), (int)T, N,
+                     reinterpret_cast<unsigned long long*>(applied.data_ptr<int64_t>()));
+  return applied;
 }
 
 }  // namespace trec_amd

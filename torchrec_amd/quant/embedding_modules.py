@@ -126,7 +126,8 @@ def dequantize_rowwise_int8(packed: torch.Tensor, D: int) -> torch.Tensor:
     """Packed rows -> fp32 [R, D] using the STORED fp16 scale/bias."""
     R = packed.shape[0]
     q = packed[:, :D].float()
-    sb = packed[:, D : D + 4].reshape(R, 2, 2).view(torch.float16).reshape(R, 2)
+    # a copy: at an odd D the scale sits at an odd byte, which cannot be viewed as fp16
+    sb = packed[:, D : D + 4].contiguous().view(torch.float16)
     scale = sb[:, 0].float()
     bias = sb[:, 1].float()
     return q * scale.unsqueeze(1) + bias.unsqueeze(1)
@@ -320,13 +321,7 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
 
     def load_float_table(self, i: int, weights: torch.Tensor) -> None:
         name, rows, dim = self._specs[i]
-        w = weights.to(self.qweights.device).float()
-        if self._formats[i] == FP8_FORMAT_CODE:
-            packed = quantize_rowwise_fp8(w)
-        elif self._bits[i] == 8:
-            packed = quantize_rowwise_int8(w)
-        else:
-            packed = quantize_rowwise_nbit(w, self._bits[i])
+        packed = self._quantize_rows(i, weights.to(self.qweights.device).float())
         start = int(self._table_byte_offsets[i])
         self.qweights[start : start + packed.numel()].copy_(packed.reshape(-1))
 
@@ -335,6 +330,160 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         start = int(self._table_byte_offsets[i])
         stride = self._stride(dim, self._formats[i])
         return self.qweights[start : start + rows * stride].view(rows, stride)
+
+    def _code_bytes(self, i: int) -> int:
+        return self._specs[i][2] * self._bits[i] // 8
+
+    def _quantize_rows(self, i: int, w: torch.Tensor) -> torch.Tensor:
+        """fp32 [n, dim] -> packed rows in table ``i``'s format (its own quantiser)."""
+        if self._formats[i] == FP8_FORMAT_CODE:
+            return quantize_rowwise_fp8(w)
+        if self._bits[i] == 8:
+            return quantize_rowwise_int8(w)
+        return quantize_rowwise_nbit(w, self._bits[i])
+
+    def _update_meta(
+        self, counts: Tuple[int, ...], windows: Tuple[Tuple[int, int], ...]
+    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(row_lo, row_hi, upd_offsets, val_offsets) on the device, built from
+        shapes alone and cached, so a repeated update of the same shape
+        uploads nothing (and can be captured in a graph after one warm-up)."""
+        dev = self._dims_t.device
+        key = (counts, windows, dev)
+        cache = self.__dict__.setdefault("_update_meta_cache", {})
+        meta = cache.get(key)
+        if meta is None:
+            upd, val = [0], []
+            v = 0
+            for n, (_, _, dim) in zip(counts, self._specs):
+                upd.append(upd[-1] + n)
+                val.append(v)
+                v += n * dim
+            i64 = lambda xs: torch.tensor(xs, dtype=torch.int64).to(dev)
+            meta = (
+                i64([w[0] for w in windows]),
+                i64([w[1] for w in windows]),
+                i64(upd),
+                i64(val),
+            )
+            if len(cache) >= 64:
+                cache.clear()
+            cache[key] = meta
+        return meta
+
+    @torch.no_grad()
+    def update_rows(
+        self,
+        updates: Dict[int, Tuple[torch.Tensor, torch.Tensor]],
+        row_windows: Optional[List[Tuple[int, int]]] = None,
+    ) -> torch.Tensor:
+        """Requantise rows of the served tables in place from float rows.
+
+        ``updates[t] = (ids [n], rows [n, dim])`` for table index ``t``; rows
+        of any float dtype are converted to fp32. ``row_windows[t] = (lo, hi)``
+        (default ``(0, rows)``) is the range of ids this module holds for
+        table ``t``: an entry with id ``r`` is applied only if ``lo <= r <
+        hi``, to local row ``r - lo``, and every other entry is dropped (on
+        the device, with no host sync). ``(0, rows)`` bounds-checks an
+        unsharded table; a shard passes its own global row range, so every
+        rank takes the same full delta and keeps its rows. An id whose local
+        row lies past the table is dropped as well. Returns int64 [T]: the
+        number of entries applied per table.
+
+        Contract (GPU: ``quant_tbe_update_rows``, one HIP kernel, one wave per
+        entry, current stream, pinned-host ``location="managed"`` tables
+        included; CPU: the CPU quantisers):
+
+        * the first ``code_bytes + 4`` bytes of an applied row are exactly
+          what the table's own quantiser (``quantize_rowwise_int8`` for INT8,
+          any ``D``; ``quantize_rowwise_nbit`` for INT4/INT2;
+          ``quantize_rowwise_fp8`` for FP8) writes for that fp32 row;
+        * no other byte of ``qweights`` changes: not the row's padding, not
+          its neighbours, not another table;
+        * ids within one table's segment must be unique (the model tracker's
+          ``UniqueRows`` are); duplicates with different values are undefined
+          on the GPU;
+        * the update is ordered against lookups on the same stream only. A
+          lookup running concurrently on another stream may see a row whose
+          codes and scale come from different versions: serialising the
+          streams is the caller's job.
+
+        Shapes are validated on the host; id values are not (that would need
+        a host sync). Nothing here reads a device value on the host, so an
+        update whose shapes were seen once before can be captured in a graph.
+        """
+        T = len(self._specs)
+        for t in updates:
+            if not isinstance(t, int) or not 0 <= t < T:
+                raise IndexError(f"update_rows: table index {t!r} is not in [0, {T})")
+        if row_windows is None:
+            row_windows = [(0, rows) for _, rows, _ in self._specs]
+        if len(row_windows) != T:
+            raise ValueError(f"row_windows has {len(row_windows)} entries for {T} tables")
+        windows = tuple((int(lo), int(hi)) for lo, hi in row_windows)
+        on_gpu = self.qweights.is_cuda or self._uvm
+        dev = self._dims_t.device if on_gpu else self.qweights.device
+        ids_l: List[torch.Tensor] = []
+        rows_l: List[torch.Tensor] = []
+        counts: List[int] = []
+        for t, (name, _, dim) in enumerate(self._specs):
+            if t not in updates:
+                counts.append(0)
+                continue
+            ids, rows = updates[t]
+            if ids.dim() != 1 or tuple(rows.shape) != (ids.numel(), dim):
+                raise ValueError(
+                    f"update_rows: table {name} takes ids [n] and rows [n, {dim}], got "
+                    f"{tuple(ids.shape)} and {tuple(rows.shape)}"
+                )
+            if not rows.is_floating_point():
+                raise ValueError(f"update_rows: table {name}: rows must be a float tensor")
+            counts.append(ids.numel())
+            ids_l.append(ids.to(device=dev, dtype=torch.int64))
+            rows_l.append(rows.to(device=dev, dtype=torch.float32))
+        if on_gpu:
+            ops.hip_ops()
+            row_lo, row_hi, upd_offsets, val_offsets = self._update_meta(tuple(counts), windows)
+            if ids_l:
+                upd_rows = torch.cat(ids_l) if len(ids_l) > 1 else ids_l[0].contiguous()
+                values = (
+                    torch.cat([r.reshape(-1) for r in rows_l])
+                    if len(rows_l) > 1
+                    else rows_l[0].contiguous().reshape(-1)
+                )
+            else:
+                upd_rows = torch.empty(0, dtype=torch.int64, device=dev)
+                values = torch.empty(0, dtype=torch.float32, device=dev)
+            return torch.ops.trec_amd.quant_tbe_update_rows(
+                self.qweights,
+                self._table_byte_offsets,
+                self._dims_t,
+                self._weight_bits_t,
+                row_lo,
+                row_hi,
+                upd_offsets,
+                upd_rows,
+                values,
+                val_offsets,
+            )
+        # CPU: the same contract with the CPU quantisers
+        applied = torch.zeros(T, dtype=torch.int64)
+        k = 0
+        for t, n in enumerate(counts):
+            if t not in updates:
+                continue
+            ids, rows = ids_l[k], rows_l[k]
+            k += 1
+            lo, hi = windows[t]
+            local = ids - lo
+            keep = (ids >= lo) & (ids < hi) & (local < self._specs[t][1])
+            applied[t] = int(keep.sum())
+            if applied[t] == 0:
+                continue
+            nb = self._code_bytes(t) + 4
+            packed = self._quantize_rows(t, rows[keep])
+            self.packed_table(t)[local[keep], :nb] = packed[:, :nb]
+        return applied
 
     def dequantized_table(self, i: int) -> torch.Tensor:
         """fp32 [rows, dim] of table ``i`` from its packed bytes."""
@@ -457,6 +606,45 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         )
 
 
+def delta_ids_rows(name: str, entry: object) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One table's entry of a model delta, a ``UniqueRows`` (model tracker) or
+    an ``(ids, rows)`` pair, as ``(ids, rows)``."""
+    if isinstance(entry, (tuple, list)):
+        ids, rows = entry
+    else:
+        ids, rows = entry.ids, entry.rows
+    if rows is None:
+        raise ValueError(
+            f"table {name}: the delta carries ids but no rows. Track with "
+            f"UpdateMode.FIRST or UpdateMode.LAST: UpdateMode.NONE records ids only"
+        )
+    return ids, rows
+
+
+def check_delta_tables(delta: Dict[str, object], served: List[str], module: str) -> None:
+    unknown = [n for n in delta if n not in served]
+    if unknown:
+        raise KeyError(f"{module} serves no table named {unknown}; it serves {list(served)}")
+
+
+def update_tbe_from_delta(
+    tbe: QuantTableBatchedEmbeddingBags,
+    delta: Dict[str, object],
+    row_windows: Optional[List[Tuple[int, int]]] = None,
+) -> Dict[str, torch.Tensor]:
+    """Apply the entries of ``delta`` whose table ``tbe`` holds (the others are
+    not its business); returns table name -> applied count (int64 scalar)."""
+    updates = {
+        i: delta_ids_rows(name, delta[name])
+        for i, (name, _, _) in enumerate(tbe._specs)
+        if name in delta
+    }
+    if not updates:
+        return {}
+    applied = tbe.update_rows(updates, row_windows)
+    return {tbe._specs[i][0]: applied[i] for i in updates}
+
+
 def _resolve_weight_dtype(
     name: str,
     weight_dtype: DataType,
@@ -539,6 +727,14 @@ class EmbeddingBagCollection(nn.Module):
     def output_dtype(self) -> torch.dtype:
         return self._output_dtype
 
+    def update_embeddings(self, delta: Dict[str, object]) -> Dict[str, torch.Tensor]:
+        """Requantise the rows of ``delta`` (table name -> the model tracker's
+        ``UniqueRows`` or ``(ids, rows)``) in place; ids outside ``[0, rows)``
+        are dropped. Returns table name -> applied count. The contract is
+        ``QuantTableBatchedEmbeddingBags.update_rows``'s."""
+        check_delta_tables(delta, [t.name for t in self._embedding_bag_configs], "this quant EBC")
+        return update_tbe_from_delta(self._tbe, delta)
+
     def forward(self, features: KeyedJaggedTensor) -> KeyedTensor:
         if features.keys() != self._feature_names:
             order = [features.keys().index(f) for f in self._feature_names]
@@ -607,6 +803,14 @@ class EmbeddingCollection(nn.Module):
 
     def output_dtype(self) -> torch.dtype:
         return self._output_dtype
+
+    def update_embeddings(self, delta: Dict[str, object]) -> Dict[str, torch.Tensor]:
+        """Requantise the rows of ``delta`` (table name -> the model tracker's
+        ``UniqueRows`` or ``(ids, rows)``) in place; ids outside ``[0, rows)``
+        are dropped. Returns table name -> applied count. The contract is
+        ``QuantTableBatchedEmbeddingBags.update_rows``'s."""
+        check_delta_tables(delta, [t.name for t in self._embedding_configs], "this quant EC")
+        return update_tbe_from_delta(self._tbe, delta)
 
     @torch.no_grad()
     def forward(self, features: KeyedJaggedTensor) -> Dict[str, JaggedTensor]:
