@@ -5,6 +5,7 @@ Run on an MI355X:
     python benchmarks/tbe_bench.py            # all suites
     python benchmarks/tbe_bench.py --suite tbe
     python benchmarks/tbe_bench.py --update-rows   # in-place row update vs table reload
+    python benchmarks/tbe_bench.py --checked       # bounds-checked / pruned quant lookup
 Prints one JSON line per measurement.
 """
 
@@ -330,10 +331,85 @@ def bench_update_rows(N=4096, D=128, rows=100_000):
         }))
 
 
+def bench_checked_suite(B=8192, D=128, tables=26, rows=100_000):
+    """What the bounds check / pruning remap in front of the quantized lookup
+    costs, at the quant bench shape. Every time is the device time of one call
+    (50 of them replayed from a graph). Per format (INT8, INT4):
+
+    * ``unchecked``: the module built without checking, five times (median +
+      max-min spread = the noise margin of this run);
+    * ``checked``: ``bounds_check=True``, no remap; ``pruned``: every odd id
+      pruned, the table at half its rows; three times each, alternating;
+    * the remap kernel alone at the lookup's id count: all ids valid (with and
+      without a remap) and all ids out of range, which is where serialised
+      counting would show."""
+    from torchrec_amd.modules.embedding_configs import DataType
+    from torchrec_amd.quant.embedding_modules import QuantTableBatchedEmbeddingBags
+
+    dev = torch.device("cuda")
+    F = tables
+    N = F * B
+    torch.manual_seed(0)
+    indices = torch.randint(0, rows, (N,)).cuda()
+    offsets = torch.arange(N + 1, dtype=torch.int64).cuda()
+    remap = torch.arange(rows, dtype=torch.int32) // 2
+    remap[1::2] = -1
+    for dt in (DataType.INT8, DataType.INT4):
+        def build(n_rows, **kw):
+            q = QuantTableBatchedEmbeddingBags(
+                [(f"t{i}", n_rows, D) for i in range(tables)], device=dev,
+                weight_dtypes=[dt] * tables, **kw,
+            )
+            for i in range(tables):
+                q.load_float_table(i, torch.randn(n_rows, D, device="cuda"))
+            return q
+
+        plain = build(rows)
+        checked = build(rows, bounds_check=True)
+        pruned = build(rows // 2, index_remapping=[remap] * tables)
+        base = [_time_graph(lambda: plain(indices, offsets)) for _ in range(5)]
+        chk, prn = [], []
+        for _ in range(3):
+            chk.append(_time_graph(lambda: checked(indices, offsets)))
+            prn.append(_time_graph(lambda: pruned(indices, offsets)))
+        med = lambda xs: sorted(xs)[len(xs) // 2]
+        runs = lambda xs: [round(t, 2) for t in xs]
+        print(json.dumps({
+            "bench": "quant_tbe_fwd_checked", "weight_dtype": dt.name, "B": B, "tables": tables,
+            "D": D, "rows": rows, "ids": N,
+            "unchecked_us": round(med(base), 2), "unchecked_us_runs": runs(base),
+            "unchecked_spread_us": round(max(base) - min(base), 2),
+            "checked_us": round(med(chk), 2), "checked_us_runs": runs(chk),
+            "pruned_half_us": round(med(prn), 2), "pruned_half_us_runs": runs(prn),
+        }))
+        if dt is not DataType.INT8:
+            continue
+        all_bad = torch.full_like(indices, rows)
+        alone = {}
+        for key, q, ids in (
+            ("valid", checked, indices), ("valid_remapped", pruned, indices),
+            ("all_out_of_range", checked, all_bad),
+        ):
+            alone[key] = [
+                _time_graph(lambda: q._remap_indices(ids, offsets, B, q._feat_table_t))
+                for _ in range(3)
+            ]
+        print(json.dumps({
+            "bench": "quant_tbe_remap_indices", "ids": N, "tables": tables,
+            **{f"{k}_us": round(med(v), 2) for k, v in alone.items()},
+            **{f"{k}_us_runs": runs(v) for k, v in alone.items()},
+            "bytes_ids_in_out": N * 16, "bytes_remap_reads": N * 4,
+            "out_of_range_counted": int(checked.out_of_range_counts().sum()),
+        }))
+
+
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--update-rows", action="store_true",
                    help="time the in-place row update against a whole-table reload, then exit")
+    p.add_argument("--checked", action="store_true",
+                   help="time the bounds-checked / pruned quantized lookup against the "
+                        "unchecked one and the remap kernel alone, then exit")
     p.add_argument("--suite", default="all",
                    choices=["all", "tbe", "tbe_sweep", "interaction", "sort",
                             "col_sum", "quant", "quant_out", "quant_fp8"])
@@ -341,6 +417,9 @@ if __name__ == "__main__":
     assert torch.cuda.is_available(), "run on a GPU box"
     if a.update_rows:
         bench_update_rows()
+        sys.exit(0)
+    if a.checked:
+        bench_checked_suite()
         sys.exit(0)
     if a.suite in ("all", "tbe"):
         bench_tbe()

@@ -19,6 +19,9 @@ from torchrec_amd.inference.modules import apply_model_delta, quantize_inference
 from torchrec_amd.models.dlrm import DLRM
 from torchrec_amd.modules.embedding_configs import DataType, EmbeddingBagConfig
 from torchrec_amd.modules.embedding_modules import EmbeddingBagCollection
+from torchrec_amd.quant.embedding_modules import (
+    EmbeddingBagCollection as QuantEmbeddingBagCollection,
+)
 from torchrec_amd.sparse.jagged_tensor import KeyedJaggedTensor
 
 
@@ -45,7 +48,12 @@ def main() -> None:
         over_arch_layer_sizes=[16, 1],
     )
     # quantize the sparse arch for serving
-    qmodel = quantize_inference_model(model, weight_dtype=DataType[args.weight_dtype])
+    # bounds_check: an id outside its table is dropped and counted on the
+    # device instead of being read (index_remapping={table: remap} would also
+    # serve pruned tables at their pruned size)
+    qmodel = quantize_inference_model(
+        model, weight_dtype=DataType[args.weight_dtype], bounds_check=True
+    )
     qmodel = qmodel.to(device)
 
     B = 8
@@ -70,6 +78,15 @@ def main() -> None:
         logits = qmodel(dense, kjt)
     print("rows updated:", {n: int(c) for n, c in applied.items()})
     print("predictions after the delta:", torch.sigmoid(logits.squeeze(-1)).cpu().tolist())
+
+    # a request with a bad id: the lookup drops it (a zero contribution) and counts it
+    bad = values.clone()
+    bad[0] = rows[0] + 7
+    with torch.no_grad():
+        qmodel(dense, KeyedJaggedTensor(keys=keys, values=bad, lengths=lengths, stride=B).to(device))
+    for m in qmodel.modules():
+        if isinstance(m, QuantEmbeddingBagCollection):
+            print("out-of-range ids per table:", m._tbe.out_of_range_counts().tolist())
 
 
 if __name__ == "__main__":

@@ -131,6 +131,7 @@ class GroupedPooledEmbeddingsLookup(nn.Module):
                     device=device,
                     weight_dtypes=[quant_data_type(t.data_type) for t in group],
                     output_dtype=self._out_torch_dtype,
+                    bounds_check=bool(fused_params.get("bounds_check", False)),
                 )
                 self._emb_modules.append(qtbe)
                 self._feature_splits.append(

@@ -16,6 +16,7 @@ from torchrec_amd.distributed.embedding import ShardedEmbeddingCollection
 from torchrec_amd.distributed.embedding_sharding import ShardedTableLocal
 from torchrec_amd.distributed.quant_embeddingbag import (
     apply_delta_to_shards,
+    with_module_bounds_check,
     with_module_output_dtype,
 )
 from torchrec_amd.distributed.types import (
@@ -53,9 +54,12 @@ class _QuantSeqLookup(nn.Module):
         outs: List[torch.Tensor] = []
         for f in range(F):
             t = qtbe._feature_table_map[f]
-            w = qtbe.dequantized_table(t)
+            w = qtbe._cpu_lookup_table(t)
             lo, hi = int(offsets[f * B]), int(offsets[(f + 1) * B])
-            outs.append(w[indices[lo:hi]])
+            idx = indices[lo:hi]
+            if qtbe._checked:
+                idx = qtbe._map_ids_cpu(t, idx)  # -1 indexes the appended zero row
+            outs.append(w[idx])
         rows = (
             torch.cat(outs, dim=0)
             if outs
@@ -77,6 +81,8 @@ class ShardedQuantEmbeddingCollection(ShardedEmbeddingCollection):
     ) -> None:
         object.__setattr__(self, "_quant_device_pre", device)
         fused_params = with_module_output_dtype(fused_params, module)
+        fused_params = with_module_bounds_check(fused_params, module, "EC")
+        object.__setattr__(self, "_quant_bounds_check_pre", bool(fused_params["bounds_check"]))
         object.__setattr__(
             self,
             "_quant_out_dtype_pre",
@@ -136,6 +142,7 @@ class ShardedQuantEmbeddingCollection(ShardedEmbeddingCollection):
             device=self._quant_device_pre,
             weight_dtypes=[quant_data_type(t.data_type) for t in tables],
             output_dtype=self._quant_out_dtype_pre,
+            bounds_check=self._quant_bounds_check_pre,
         )
         lookup = _QuantSeqLookup(qtbe, D)
         lookup._real_rows = [t.local_rows for t in tables]

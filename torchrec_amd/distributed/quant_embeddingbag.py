@@ -46,6 +46,29 @@ def with_module_output_dtype(
     return fused_params
 
 
+def with_module_bounds_check(
+    fused_params: Optional[Dict[str, Any]], module: Any, kind: str
+) -> Dict[str, Any]:
+    """``fused_params`` with ``bounds_check`` defaulting to the unsharded quant
+    module's setting: the local quant TBEs of a checked module are built
+    checked, so a local id past a shard's rows is dropped and counted on the
+    rank that holds the shard. Pruned tables are not sharded yet."""
+    pruned = [
+        name
+        for (name, _, _), ro in zip(module._tbe._specs, getattr(module._tbe, "_remap_offsets_t", []))
+        if int(ro) >= 0
+    ]
+    if pruned:
+        raise NotImplementedError(
+            f"sharding a quant {kind} with pruned tables (index_remapping on {pruned}) "
+            f"is not supported yet"
+        )
+    fused_params = dict(fused_params or {})
+    if "bounds_check" not in fused_params:
+        fused_params["bounds_check"] = bool(module._tbe._checked)
+    return fused_params
+
+
 def apply_delta_to_shards(
     shards: Iterable[Tuple[QuantTableBatchedEmbeddingBags, List[Tuple[int, int]]]],
     delta: Dict[str, Any],
@@ -74,6 +97,7 @@ class ShardedQuantEmbeddingBagCollection(ShardedEmbeddingBagCollection):
         device: Optional[torch.device] = None,
     ) -> None:
         fused_params = with_module_output_dtype(fused_params, module)
+        fused_params = with_module_bounds_check(fused_params, module, "EBC")
         super().__init__(module, table_name_to_parameter_sharding, env, fused_params, device)
         # load packed rows into the quant lookups (TW: whole table; RW: row slice)
         src = module._tbe

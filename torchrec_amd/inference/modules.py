@@ -29,30 +29,38 @@ def quantize_inference_model(
     output_dtype: torch.dtype = torch.float32,
     weight_dtype: DataType = DataType.INT8,
     per_table_weight_dtype: Optional[Dict[str, DataType]] = None,
+    bounds_check: bool = False,
+    index_remapping: Optional[Dict[str, torch.Tensor]] = None,
 ) -> nn.Module:
     """Swap float embedding modules for rowwise-quantized ones in-place
     (reference inference/modules.py:372). Tables are packed at
     ``weight_dtype`` (INT8/INT4/INT2/FP8) unless ``per_table_weight_dtype``
-    names another format for them."""
+    names another format for them.
+
+    ``bounds_check`` makes every quantized module drop (and count) ids outside
+    its tables instead of reading them; ``index_remapping`` (table name ->
+    int32/int64 ``[num_embeddings]`` tensor of physical rows, -1 = pruned)
+    serves the named tables pruned. Both are
+    ``QuantTableBatchedEmbeddingBags``'s arguments, by table name."""
     mapping = quantization_mapping or {
         FloatEBC: QuantEBC,
         FloatEC: QuantEC,
     }
+    # custom mappings only need the original from_float signature: an
+    # argument is passed on only when it is set
+    kwargs: Dict[str, Any] = {}
+    if weight_dtype != DataType.INT8 or per_table_weight_dtype:
+        kwargs.update(weight_dtype=weight_dtype, per_table_weight_dtype=per_table_weight_dtype)
+    if bounds_check:
+        kwargs["bounds_check"] = True
+    if index_remapping:
+        kwargs["index_remapping"] = index_remapping
 
     def _swap(parent: nn.Module) -> None:
         for name, child in list(parent.named_children()):
             qcls = mapping.get(type(child))
             if qcls is not None:
-                if weight_dtype == DataType.INT8 and not per_table_weight_dtype:
-                    # custom mappings only need the original from_float signature
-                    q = qcls.from_float(child, output_dtype=output_dtype)
-                else:
-                    q = qcls.from_float(
-                        child,
-                        output_dtype=output_dtype,
-                        weight_dtype=weight_dtype,
-                        per_table_weight_dtype=per_table_weight_dtype,
-                    )
+                q = qcls.from_float(child, output_dtype=output_dtype, **kwargs)
                 setattr(parent, name, q)
             else:
                 _swap(child)

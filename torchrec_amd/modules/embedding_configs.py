@@ -156,6 +156,9 @@ class BaseEmbeddingConfig:
     # space; physical capacity and eviction ride the policy config
     use_virtual_table: bool = False
     virtual_table_eviction_policy: Optional[VirtualTableEvictionPolicy] = None
+    # pruned tables (quantized inference): num_embeddings stays the LOGICAL id
+    # space; this is the number of physical rows kept after pruning
+    num_embeddings_post_pruning: Optional[int] = None
 
     def get_weight_init_max(self) -> float:
         if self.weight_init_max is None:

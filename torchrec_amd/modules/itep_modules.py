@@ -63,6 +63,17 @@ class GenericITEPModule(nn.Module):
     def pruned_size(self, table: str) -> int:
         return self._pruned_sizes[table]
 
+    def index_remapping(self, table: str) -> torch.Tensor:
+        """The eval-time mapping of ``remap_table`` as one int64
+        [unpruned] tensor: unmapped ids point at the sacrificial last row, so
+        there is no -1. A quantized EBC built from the float EBC with it
+        (``index_remapping={table: ...}``) serves what this module's wrapper
+        computes in eval."""
+        lookup = getattr(self, f"_lookup_{table}")
+        return torch.where(
+            lookup < 0, torch.full_like(lookup, self._pruned_sizes[table] - 1), lookup
+        )
+
     def remap_table(self, table: str, values: torch.Tensor) -> torch.Tensor:
         lookup = getattr(self, f"_lookup_{table}")
         util = getattr(self, f"_util_{table}")

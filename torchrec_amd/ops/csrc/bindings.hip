@@ -138,6 +138,11 @@ at::Tensor tbe_forward_seq_nbit(const at::Tensor& qweights,
                                 const at::Tensor& weight_bits, const at::Tensor& feat_table,
                                 const at::Tensor& feat_val_offsets, const at::Tensor& indices,
                                 int64_t D_out, int64_t max_units, int64_t output_dtype);
+at::Tensor quant_tbe_remap_indices(const at::Tensor& indices, const at::Tensor& seg_offsets,
+                                   int64_t seg_stride, const at::Tensor& feat_table,
+                                   const at::Tensor& logical_rows,
+                                   const at::Tensor& remap_offsets, const at::Tensor& remap,
+                                   at::Tensor oob_counts);
 at::Tensor quant_tbe_update_rows(at::Tensor qweights, const at::Tensor& table_byte_offsets,
                                  const at::Tensor& dims, const at::Tensor& weight_bits,
                                  const at::Tensor& row_lo, const at::Tensor& row_hi,
@@ -290,6 +295,10 @@ TORCH_LIBRARY(trec_amd, m) {
       "quant_tbe_update_rows(Tensor(a!) qweights, Tensor table_byte_offsets, Tensor dims,"
       " Tensor weight_bits, Tensor row_lo, Tensor row_hi, Tensor upd_offsets, Tensor upd_rows,"
       " Tensor values, Tensor val_offsets) -> Tensor");
+  m.def(
+      "quant_tbe_remap_indices(Tensor indices, Tensor seg_offsets, int seg_stride,"
+      " Tensor feat_table, Tensor logical_rows, Tensor remap_offsets, Tensor remap,"
+      " Tensor(a!) oob_counts) -> Tensor");
   m.def("col_sum(Tensor input) -> Tensor");
   m.def("interaction_forward(Tensor dense, Tensor sparse, Tensor pi, Tensor pj) -> Tensor");
   m.def("relu_bwd_col_sum(Tensor grad_out, Tensor y) -> (Tensor, Tensor)");
@@ -346,6 +355,7 @@ TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
   m.impl("tbe_forward_pooled_nbit", trec_amd::tbe_forward_pooled_nbit);
   m.impl("tbe_forward_seq_nbit", trec_amd::tbe_forward_seq_nbit);
   m.impl("quant_tbe_update_rows", trec_amd::quant_tbe_update_rows);
+  m.impl("quant_tbe_remap_indices", trec_amd::quant_tbe_remap_indices);
   m.impl("col_sum", trec_amd::col_sum);
   m.impl("interaction_forward", trec_amd::interaction_forward);
   m.impl("relu_bwd_col_sum", trec_amd::relu_bwd_col_sum);

@@ -27,6 +27,7 @@
 #include <hip/hip_fp16.h>
 
 #include "common.h"
+#include "quant_remap.h"
 
 namespace trec_amd {
 
@@ -908,6 +909,144 @@ at::Tensor quant_tbe_update_rows(
                      values.data_ptr<float>(), val_offsets.data_ptr<int64_t>(), (int)T, N,
                      reinterpret_cast<unsigned long long*>(applied.data_ptr<int64_t>()));
   return applied;
+}
+
+// ===========================================================================
+// Bounds check and pruning remap of a lookup's ids, in front of the four
+// forward kernels and of quant_tbe_update_rows (reference
+// IntNBitTableBatchedEmbeddingBags: index_remapping + bounds check).
+//
+// Contract:
+//  * out[n] is the physical row of indices[n], or -1 where the id is dropped:
+//    an id outside [0, logical_rows[t]) of its table t, or one whose remap
+//    entry is -1 (pruned). The per-id decision is quant_remap_id
+//    (quant_remap.h). indices is never written.
+//  * Id n belongs to segment f where seg_offsets[f * seg_stride] <= n <
+//    seg_offsets[(f + 1) * seg_stride], f in [0, F), and to table
+//    feat_table[f]. The pooled path hands in the KJT offsets [F*B+1] with
+//    stride B, the sequence path feat_val_offsets [F+1] with stride 1, the
+//    row update upd_offsets [T+1] with stride 1 and feat_table = arange(T).
+//  * remap_offsets[t] is the start of table t's int32 [logical_rows[t]]
+//    segment in remap, or -1 where the table has none. remap is read only at
+//    an id that passed the range test.
+//  * oob_counts[t] += the out-of-range ids of table t (cumulative; pruned ids
+//    are ordinary traffic and are not counted).
+//  * A table built for checking has an all-zero row in front of its rows, so
+//    the lookups read row -1 as zeros in every format and add weight * 0.
+//  * No host read: capturable in a graph.
+//
+// Lane mapping: one thread per id, grid-stride, so a wave reads 64
+// consecutive ids (512 B) and writes 64 consecutive rows. The segment search
+// reads F+1 strided words that stay in cache; the remap read is a gather.
+// Traffic: N * 16 B (id in, row out) + 4 B per remapped id.
+//
+// Counting: atomics on one address serialise (54 us for 4096 of them in the
+// update kernel above). Out-of-range ids are summed per wave where the wave's
+// bad ids share a table (ids arrive sorted by feature, so they nearly always
+// do), then per block in an LDS table, and one lane issues one vector
+// atomicAdd per table and block. Only T > kRemapLdsTables counts with direct
+// global atomics.
+// ===========================================================================
+
+constexpr int kRemapLdsTables = 1024;
+
+__device__ __forceinline__ int upper_bound_segment_strided(const int64_t* offs, int64_t stride,
+                                                           int n, int64_t x) {
+  int lo = 0, hi = n;  // invariant: offs[lo*stride] <= x < offs[hi*stride]
+  while (hi - lo > 1) {
+    int mid = (lo + hi) >> 1;
+    if (offs[mid * stride] <= x) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+__global__ void __launch_bounds__(kBlockThreads) quant_tbe_remap_indices_kernel(
+    const int64_t* __restrict__ indices,      // [N]
+    const int64_t* __restrict__ seg_offsets,  // [F*seg_stride + 1]
+    int64_t seg_stride,
+    const int32_t* __restrict__ feat_table,     // [F]
+    const int64_t* __restrict__ logical_rows,   // [T]
+    const int64_t* __restrict__ remap_offsets,  // [T], -1: no remap
+    const int32_t* __restrict__ remap, int F, int T, int64_t N, int64_t* __restrict__ out,
+    unsigned long long* __restrict__ oob_counts) {
+  __shared__ unsigned int s_oob[kRemapLdsTables];
+  const bool use_lds = T <= kRemapLdsTables;
+  if (use_lds) {
+    for (int t = threadIdx.x; t < T; t += kBlockThreads) s_oob[t] = 0u;
+    __syncthreads();
+  }
+  int l = lane_id();
+  int64_t step = static_cast<int64_t>(gridDim.x) * kBlockThreads;
+  // every lane of a wave makes the same number of trips (the ballots below
+  // need the whole wave): the bound is on the wave's first id
+  int64_t first = static_cast<int64_t>(blockIdx.x) * kBlockThreads + (threadIdx.x - l);
+  for (int64_t base = first; base < N; base += step) {
+    int64_t n = base + l;
+    bool bad = false;
+    int t = 0;
+    if (n < N) {
+      int64_t idx = indices[n];
+      int f = upper_bound_segment_strided(seg_offsets, seg_stride, F, n);
+      t = feat_table[f];
+      int64_t ro = remap_offsets[t];
+      out[n] = quant_remap_id(idx, logical_rows[t], (ro >= 0 && remap) ? remap + ro : nullptr,
+                              &bad);
+    }
+    unsigned long long bad_mask = __ballot(bad);
+    if (bad_mask == 0ull) continue;
+    int leader = __ffsll(bad_mask) - 1;
+    int t0 = __shfl(t, leader, kWaveSize);
+    if (!use_lds) {
+      if (bad) atomicAdd(oob_counts + t, 1ull);
+    } else if (__ballot(bad && t == t0) == bad_mask) {
+      if (l == leader) atomicAdd(&s_oob[t0], static_cast<unsigned int>(__popcll(bad_mask)));
+    } else if (bad) {
+      atomicAdd(&s_oob[t], 1u);
+    }
+  }
+  if (use_lds) {
+    __syncthreads();
+    for (int t = threadIdx.x; t < T; t += kBlockThreads) {
+      unsigned int c = s_oob[t];
+      if (c != 0u) atomicAdd(oob_counts + t, static_cast<unsigned long long>(c));
+    }
+  }
+}
+
+at::Tensor quant_tbe_remap_indices(
+    const at::Tensor& indices, const at::Tensor& seg_offsets, int64_t seg_stride,
+    const at::Tensor& feat_table, const at::Tensor& logical_rows,
+    const at::Tensor& remap_offsets, const at::Tensor& remap, at::Tensor oob_counts) {
+  const char* op = "quant_tbe_remap_indices: ";
+  auto on_dev = [](const at::Tensor& t, at::ScalarType st) {
+    return t.is_cuda() && t.scalar_type() == st && t.is_contiguous();
+  };
+  int64_t N = indices.numel();
+  int64_t F = feat_table.numel();
+  int64_t T = logical_rows.numel();
+  TORCH_CHECK(on_dev(indices, at::kLong) && indices.dim() == 1, op,
+              "indices must be contiguous int64 [N] on the device");
+  TORCH_CHECK(on_dev(feat_table, at::kInt), op, "feat_table must be int32 [F] on the device");
+  TORCH_CHECK(seg_stride >= 1 && on_dev(seg_offsets, at::kLong) &&
+                  seg_offsets.numel() >= F * seg_stride + 1,
+              op, "seg_offsets must be int64 with at least F * seg_stride + 1 entries");
+  TORCH_CHECK(on_dev(logical_rows, at::kLong) && on_dev(remap_offsets, at::kLong) &&
+                  remap_offsets.numel() == T && on_dev(oob_counts, at::kLong) &&
+                  oob_counts.numel() == T,
+              op, "logical_rows, remap_offsets and oob_counts must be int64 [T] on the device");
+  TORCH_CHECK(remap.numel() == 0 || on_dev(remap, at::kInt), op,
+              "remap must be int32 on the device");
+  auto out = at::empty_like(indices);
+  if (N == 0) return out;
+  TORCH_CHECK(F > 0 && T > 0, op, "ids without a feature or a table");
+  hipLaunchKernelGGL(quant_tbe_remap_indices_kernel, dim3(grid_for(N, kBlockThreads)),
+                     dim3(kBlockThreads), 0, q_stream(), indices.data_ptr<int64_t>(),
+                     seg_offsets.data_ptr<int64_t>(), seg_stride, feat_table.data_ptr<int32_t>(),
+                     logical_rows.data_ptr<int64_t>(), remap_offsets.data_ptr<int64_t>(),
+                     remap.numel() > 0 ? remap.data_ptr<int32_t>() : nullptr, (int)F, (int)T, N,
+                     out.data_ptr<int64_t>(),
+                     reinterpret_cast<unsigned long long*>(oob_counts.data_ptr<int64_t>()));
+  return out;
 }
 
 }  // namespace trec_amd

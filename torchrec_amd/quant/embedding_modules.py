@@ -237,7 +237,34 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
     all INT8). GPU path = tbe_forward_pooled_int8 when every table is INT8, else
     tbe_forward_pooled_nbit (one launch for mixed formats); CPU path = dequant
     reference. ``output_dtype`` (fp32 / bf16 / fp16) is the dtype of every
-    lookup's result: the arithmetic is fp32 and the value is rounded once."""
+    lookup's result: the arithmetic is fp32 and the value is rounded once.
+
+    ``bounds_check`` / ``index_remapping`` (checking; off by default). With
+    checking on, every lookup first runs ``quant_tbe_remap_indices`` (one HIP
+    launch, no host read, capturable in a graph) over its ids and hands the
+    result, a new int64 tensor, to the unchanged lookup op; the caller's ids
+    are never written. An id outside ``[0, logical rows)`` of its table is
+    dropped and counted (``out_of_range_counts()``); it is NOT clamped, which
+    would serve another item's embedding. ``index_remapping[t]`` (int32/int64
+    ``[logical_rows]``, values in ``[-1, rows)``) serves a pruned table:
+    ``specs[t][1]`` stays the physical row count, the logical id space is
+    ``len(index_remapping[t])``, and an id mapped to -1 is dropped without
+    being counted. A remap on any table turns checking on. A dropped id
+    contributes zero to a pooled lookup (MEAN still divides by the full bag
+    length, the reference's semantics for pruned ids) and is a zero row of a
+    sequence lookup. Per-sample weights are assumed finite: a dropped id is
+    ``weight * 0``, and ``NaN * 0`` is NaN.
+
+    Layout with checking on: each table is ``[one all-zero row][rows...]`` and
+    the table's byte offset points past the zero row, so the lookup kernels
+    (signed 64-bit ``id * stride``) read id -1 as zero bytes, which dequantise
+    to 0 in every format. ``qweights`` is ``sum(stride_t)`` bytes larger than
+    an unchecked module's, ``packed_table(i)`` is still the ``[rows, stride]``
+    view without the zero row, and no zero row is ever written. A checked and
+    an unchecked module do not exchange ``state_dict``s (the buffer sizes
+    differ, and a pruned module also carries ``index_remap``). A module built
+    without checking has the byte layout, ``state_dict``, launches and results
+    it had before these arguments existed."""
 
     def __init__(
         self,
@@ -248,6 +275,8 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         location: str = "device",  # "device" (HBM) | "managed" (pinned host, QUANT_UVM)
         weight_dtypes: Optional[List[DataType]] = None,
         output_dtype: torch.dtype = torch.float32,
+        bounds_check: bool = False,
+        index_remapping: Optional[List[Optional[torch.Tensor]]] = None,
     ) -> None:
         super().__init__()
         if output_dtype not in _OUT_DTYPE_CODE:
@@ -284,9 +313,22 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         F = len(self._feature_table_map)
         self._num_features = F
         self.pooling = pooling
-        byte_offsets = [0]
+        remaps = self._check_index_remapping(specs, index_remapping)
+        self._checked = bool(bounds_check) or any(r is not None for r in remaps)
+        self._has_remap = any(r is not None for r in remaps)
+        self._logical_rows = [
+            rows if r is None else r.numel() for (_, rows, _), r in zip(specs, remaps)
+        ]
+        # table_starts[t] is where table t's rows begin; with checking on an
+        # all-zero row sits in front of them (row -1 of the table)
+        table_starts = []
+        end = 0
         for (_, rows, dim), b in zip(specs, self._formats):
-            byte_offsets.append(byte_offsets[-1] + rows * self._stride(dim, b))
+            stride = self._stride(dim, b)
+            start = end + (stride if self._checked else 0)
+            table_starts.append(start)
+            end = start + rows * stride
+        byte_offsets = table_starts + [end]
         dims = [s[2] for s in specs]
         feat_dims = [dims[t] for t in self._feature_table_map]
         d_out = [0]
@@ -310,6 +352,116 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         reg("_feat_table_t", torch.tensor(self._feature_table_map, dtype=torch.int32))
         reg("_d_out_offsets", torch.tensor(d_out, dtype=torch.int64))
         reg("_empty_f", torch.empty(0, dtype=torch.float32))
+        if self._checked:
+            remap_offsets, flat, n = [], [], 0
+            for r in remaps:
+                remap_offsets.append(-1 if r is None else n)
+                if r is not None:
+                    flat.append(r.to(torch.int32).cpu())
+                    n += r.numel()
+            reg("_logical_rows_t", torch.tensor(self._logical_rows, dtype=torch.int64))
+            reg("_remap_offsets_t", torch.tensor(remap_offsets, dtype=torch.int64))
+            reg("_table_ids_t", torch.arange(T, dtype=torch.int32))
+            reg("_oob_counts", torch.zeros(T, dtype=torch.int64))
+            if self._has_remap:
+                # part of the served model: persistent, and registered only
+                # here, so the state_dict of a module without a remap is the
+                # one it always had
+                self.register_buffer("index_remap", torch.cat(flat).to(device))
+            else:
+                reg("_empty_i32", torch.empty(0, dtype=torch.int32))
+
+    @staticmethod
+    def _check_index_remapping(
+        specs: List[Tuple[str, int, int]],
+        index_remapping: Optional[List[Optional[torch.Tensor]]],
+    ) -> List[Optional[torch.Tensor]]:
+        """Host-side validation at construction: one entry per table, each
+        None or an int32/int64 [logical_rows] tensor with values in [-1, rows)."""
+        if index_remapping is None:
+            return [None] * len(specs)
+        if len(index_remapping) != len(specs):
+            raise ValueError(
+                f"index_remapping has {len(index_remapping)} entries for {len(specs)} tables"
+            )
+        out: List[Optional[torch.Tensor]] = []
+        for (name, rows, _), r in zip(specs, index_remapping):
+            if r is None:
+                out.append(None)
+                continue
+            if not isinstance(r, torch.Tensor) or r.dtype not in (torch.int32, torch.int64):
+                raise ValueError(
+                    f"table {name}: index_remapping must be an int32 or int64 tensor, got "
+                    f"{getattr(r, 'dtype', type(r))}"
+                )
+            if r.dim() != 1:
+                raise ValueError(
+                    f"table {name}: index_remapping must be 1-D [logical_rows], got "
+                    f"{tuple(r.shape)}"
+                )
+            r = r.detach().cpu()
+            if r.numel() and (int(r.min()) < -1 or int(r.max()) >= rows):
+                raise ValueError(
+                    f"table {name}: index_remapping values must lie in [-1, {rows}) "
+                    f"(rows = the table's physical row count), got [{int(r.min())}, "
+                    f"{int(r.max())}]"
+                )
+            out.append(r)
+        return out
+
+    def _remap(self) -> torch.Tensor:
+        return self.index_remap if self._has_remap else self._empty_i32
+
+    def _remap_indices(
+        self, indices: torch.Tensor, seg_offsets: torch.Tensor, seg_stride: int,
+        feat_table: torch.Tensor,
+    ) -> torch.Tensor:
+        """GPU: logical ids -> physical rows, -1 for a dropped id (a new tensor)."""
+        if indices.numel() == 0:
+            return indices
+        return torch.ops.trec_amd.quant_tbe_remap_indices(
+            indices,
+            seg_offsets,
+            seg_stride,
+            feat_table,
+            self._logical_rows_t,
+            self._remap_offsets_t,
+            self._remap(),
+            self._oob_counts,
+        )
+
+    def _map_ids_cpu(self, t: int, idx: torch.Tensor) -> torch.Tensor:
+        """CPU: the same mapping for ids of table ``t``, in torch."""
+        idx = idx.to(torch.int64)
+        ok = (idx >= 0) & (idx < self._logical_rows[t])
+        self._oob_counts[t] += int((~ok).sum())
+        ro = int(self._remap_offsets_t[t])
+        if ro >= 0:
+            seg = self.index_remap[ro : ro + self._logical_rows[t]].to(torch.int64)
+            mapped = seg[torch.where(ok, idx, torch.zeros_like(idx))]
+        else:
+            mapped = idx
+        return torch.where(ok, mapped, torch.full_like(idx, -1))
+
+    def _cpu_lookup_table(self, t: int) -> torch.Tensor:
+        """fp32 table for the CPU reference; with checking on a zero row is
+        appended, which is where id -1 (a dropped id) indexes."""
+        w = self.dequantized_table(t)
+        if self._checked:
+            w = torch.cat([w, w.new_zeros(1, w.shape[1])])
+        return w
+
+    def out_of_range_counts(self) -> torch.Tensor:
+        """Cumulative int64 [T]: ids outside ``[0, logical rows)`` seen per
+        table by lookups (and by ``update_rows`` of a pruned module) since
+        construction or the last reset. Pruned ids are not counted. The
+        tensor lives on the device and reading it here syncs nothing."""
+        if not self._checked:
+            raise RuntimeError("this module was built without bounds_check / index_remapping")
+        return self._oob_counts
+
+    def reset_out_of_range_counts(self) -> None:
+        self.out_of_range_counts().zero_()
 
     @staticmethod
     def _stride(dim: int, bits: int) -> int:
@@ -321,6 +473,11 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
 
     def load_float_table(self, i: int, weights: torch.Tensor) -> None:
         name, rows, dim = self._specs[i]
+        if self._checked and tuple(weights.shape) != (rows, dim):
+            # a longer table would run into the next table's zero row
+            raise ValueError(
+                f"table {name} holds [{rows}, {dim}] rows, got {tuple(weights.shape)}"
+            )
         packed = self._quantize_rows(i, weights.to(self.qweights.device).float())
         start = int(self._table_byte_offsets[i])
         self.qweights[start : start + packed.numel()].copy_(packed.reshape(-1))
@@ -408,6 +565,14 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
           codes and scale come from different versions: serialising the
           streams is the caller's job.
 
+        On a module built with checking the zero rows are never written:
+        every window is clamped to ``0 <= lo`` and ``hi <= lo + rows``. On a
+        module with an ``index_remapping`` the ids are LOGICAL ids: they go
+        through ``quant_tbe_remap_indices`` first (the segments are the
+        tables), an entry for a pruned or out-of-range id is dropped and not
+        counted as applied, out-of-range ones add to
+        ``out_of_range_counts()``, and the windows apply to the physical rows.
+
         Shapes are validated on the host; id values are not (that would need
         a host sync). Nothing here reads a device value on the host, so an
         update whose shapes were seen once before can be captured in a graph.
@@ -421,6 +586,11 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         if len(row_windows) != T:
             raise ValueError(f"row_windows has {len(row_windows)} entries for {T} tables")
         windows = tuple((int(lo), int(hi)) for lo, hi in row_windows)
+        if self._checked:
+            windows = tuple(
+                (max(lo, 0), min(hi, max(lo, 0) + rows))
+                for (lo, hi), (_, rows, _) in zip(windows, self._specs)
+            )
         on_gpu = self.qweights.is_cuda or self._uvm
         dev = self._dims_t.device if on_gpu else self.qweights.device
         ids_l: List[torch.Tensor] = []
@@ -454,6 +624,8 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
             else:
                 upd_rows = torch.empty(0, dtype=torch.int64, device=dev)
                 values = torch.empty(0, dtype=torch.float32, device=dev)
+            if self._has_remap:
+                upd_rows = self._remap_indices(upd_rows, upd_offsets, 1, self._table_ids_t)
             return torch.ops.trec_amd.quant_tbe_update_rows(
                 self.qweights,
                 self._table_byte_offsets,
@@ -475,6 +647,8 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
             ids, rows = ids_l[k], rows_l[k]
             k += 1
             lo, hi = windows[t]
+            if self._has_remap:
+                ids = self._map_ids_cpu(t, ids)
             local = ids - lo
             keep = (ids >= lo) & (ids < hi) & (local < self._specs[t][1])
             applied[t] = int(keep.sum())
@@ -504,6 +678,8 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         B = (offsets.numel() - 1) // self._num_features
         if self.qweights.is_cuda or (self.qweights.is_pinned() and indices.is_cuda):
             ops.hip_ops()
+            if self._checked:
+                indices = self._remap_indices(indices, offsets, max(B, 1), self._feat_table_t)
             if not self._all_int8:
                 return torch.ops.trec_amd.tbe_forward_pooled_nbit(
                     self.qweights,
@@ -539,9 +715,12 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         # CPU reference
         outs = []
         for f, t in enumerate(self._feature_table_map):
-            w = self.dequantized_table(t)
+            w = self._cpu_lookup_table(t)
             off = offsets[f * B : (f + 1) * B + 1] - offsets[f * B]
             idx = indices[int(offsets[f * B]) : int(offsets[(f + 1) * B])]
+            if self._checked:
+                idx = self._map_ids_cpu(t, idx)
+                idx = torch.where(idx < 0, torch.full_like(idx, w.shape[0] - 1), idx)
             pw = (
                 per_sample_weights[int(offsets[f * B]) : int(offsets[(f + 1) * B])]
                 if per_sample_weights is not None
@@ -578,8 +757,13 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
         self, indices: torch.Tensor, feat_val_offsets: torch.Tensor, dim: int
     ) -> torch.Tensor:
         """GPU per-row lookup [N, dim]: tbe_forward_seq_int8 when every table is
-        INT8, else tbe_forward_seq_nbit. ``feat_val_offsets`` is [F+1]."""
+        INT8, else tbe_forward_seq_nbit. ``feat_val_offsets`` is [F+1]. A
+        module whose tables are on the CPU answers from the dequantised tables."""
+        if not (self.qweights.is_cuda or (self.qweights.is_pinned() and indices.is_cuda)):
+            return self.to_output_dtype(self._sequence_rows_cpu(indices, feat_val_offsets, dim))
         ops.hip_ops()
+        if self._checked:
+            indices = self._remap_indices(indices, feat_val_offsets, 1, self._feat_table_t)
         if not self._all_int8:
             return torch.ops.trec_amd.tbe_forward_seq_nbit(
                 self.qweights,
@@ -604,6 +788,22 @@ class QuantTableBatchedEmbeddingBags(nn.Module):
             self._max_D,
             self._out_dtype_code,
         )
+
+
+    def _sequence_rows_cpu(
+        self, indices: torch.Tensor, feat_val_offsets: torch.Tensor, dim: int
+    ) -> torch.Tensor:
+        """CPU reference of the sequence lookup, fp32 [N, dim]."""
+        fvo = feat_val_offsets.tolist()
+        rows_l = []
+        for f, t in enumerate(self._feature_table_map):
+            idx = indices[fvo[f] : fvo[f + 1]]
+            if idx.numel() == 0:
+                continue
+            if self._checked:
+                idx = self._map_ids_cpu(t, idx)  # -1 indexes the appended zero row
+            rows_l.append(self._cpu_lookup_table(t)[idx])
+        return torch.cat(rows_l, dim=0) if rows_l else torch.empty(0, dim)
 
 
 def delta_ids_rows(name: str, entry: object) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -658,9 +858,127 @@ def _resolve_weight_dtype(
     return dt
 
 
+def _remap_physical_rows(name: str, remap: object, logical: Optional[int]) -> int:
+    """The physical row count a table's remap addresses, ``max + 1``, after
+    the checks that need no table: an int32/int64 [logical] tensor, no value
+    below -1."""
+    if not isinstance(remap, torch.Tensor) or remap.dtype not in (torch.int32, torch.int64):
+        raise ValueError(
+            f"table {name}: index_remapping must be an int32 or int64 tensor, got "
+            f"{getattr(remap, 'dtype', type(remap))}"
+        )
+    if remap.dim() != 1 or (logical is not None and remap.numel() != logical):
+        raise ValueError(
+            f"table {name}: index_remapping must have one entry per logical id "
+            f"([{logical}]), got {tuple(remap.shape)}"
+        )
+    if remap.numel() == 0:
+        return 0
+    if int(remap.min()) < -1:
+        raise ValueError(
+            f"table {name}: index_remapping values must be -1 (pruned) or a physical "
+            f"row, got {int(remap.min())}"
+        )
+    return int(remap.max()) + 1
+
+
+def _tbe_pruning_args(
+    tables: List[object], index_remapping: Optional[Dict[str, torch.Tensor]], module: str
+) -> Tuple[List[Tuple[str, int, int]], Optional[List[Optional[torch.Tensor]]]]:
+    """(specs with PHYSICAL row counts, per-table remaps or None) for the TBE
+    behind a quant EBC / EC. ``num_embeddings`` is the logical id space, so a
+    remap has that many entries; ``num_embeddings_post_pruning``, where set,
+    must be the remap's physical row count."""
+    index_remapping = index_remapping or {}
+    unknown = [n for n in index_remapping if n not in [t.name for t in tables]]
+    if unknown:
+        raise KeyError(f"index_remapping names {unknown}, which {module} does not serve")
+    specs, remaps = [], []
+    for t in tables:
+        r = index_remapping.get(t.name)
+        post = getattr(t, "num_embeddings_post_pruning", None)
+        if r is None:
+            if post is not None and post != t.num_embeddings:
+                raise ValueError(
+                    f"table {t.name}: num_embeddings_post_pruning={post} of "
+                    f"{t.num_embeddings} rows needs an index_remapping"
+                )
+            rows = t.num_embeddings
+        else:
+            rows = _remap_physical_rows(t.name, r, t.num_embeddings)
+            if post is not None and post != rows:
+                raise ValueError(
+                    f"table {t.name}: num_embeddings_post_pruning={post} but its "
+                    f"index_remapping addresses {rows} physical rows"
+                )
+            if post is not None:
+                rows = post
+        specs.append((t.name, rows, t.embedding_dim))
+        remaps.append(r)
+    return specs, (remaps if any(r is not None for r in remaps) else None)
+
+
+def _float_rows_for_remap(name: str, weight: torch.Tensor, remap: torch.Tensor) -> torch.Tensor:
+    """The physical rows of a pruned table from its float table. A float table
+    with ``len(remap)`` rows is logical: physical row ``j`` is the float row
+    of the one id mapped to ``j``. One with the physical row count is taken
+    as it is (many ids may share a row: the in-training pruning case)."""
+    rows = _remap_physical_rows(name, remap, None)
+    n = weight.shape[0]
+    if n == remap.numel():
+        r = remap.to(torch.int64).cpu()
+        kept = (r >= 0).nonzero().flatten()
+        per_row = torch.bincount(r[kept], minlength=rows)
+        if bool((per_row != 1).any()):
+            j = int((per_row != 1).nonzero()[0])
+            raise ValueError(
+                f"table {name}: the float table is logical ({n} rows), so every physical "
+                f"row needs exactly one id, but row {j} has {int(per_row[j])}"
+            )
+        src = torch.empty(rows, dtype=torch.int64)
+        src[r[kept]] = kept
+        return weight[src.to(weight.device)]
+    if n == rows:
+        return weight
+    raise ValueError(
+        f"table {name}: the float table has {n} rows, neither the remap's logical "
+        f"{remap.numel()} nor its physical {rows}"
+    )
+
+
+def _quant_configs_for_remap(tables: List[object], index_remapping: Dict[str, torch.Tensor]):
+    """from_float: a remapped table's config gets the logical id space and the
+    physical row count of its remap."""
+    out = []
+    for t in tables:
+        r = index_remapping.get(t.name)
+        if r is not None:
+            rows = _remap_physical_rows(t.name, r, None)
+            post = getattr(t, "num_embeddings_post_pruning", None)
+            if post is not None and post != rows:
+                raise ValueError(
+                    f"table {t.name}: num_embeddings_post_pruning={post} but its "
+                    f"index_remapping addresses {rows} physical rows"
+                )
+            t = dataclasses.replace(
+                t,
+                num_embeddings=r.numel(),
+                num_embeddings_post_pruning=_remap_physical_rows(t.name, r, None),
+            )
+        out.append(t)
+    return out
+
+
 class EmbeddingBagCollection(nn.Module):
     """Quantized EBC (reference quant/embedding_modules.py:346). Each table is
-    served at its config's ``data_type`` when that is INT8/INT4/INT2/FP8, else INT8."""
+    served at its config's ``data_type`` when that is INT8/INT4/INT2/FP8, else INT8.
+
+    ``bounds_check`` and ``index_remapping`` (table name -> int32/int64
+    ``[num_embeddings]`` tensor of physical rows, -1 = pruned) are
+    ``QuantTableBatchedEmbeddingBags``'s arguments by table name:
+    ``num_embeddings`` stays the logical id space and
+    ``num_embeddings_post_pruning``, where set, must be the remap's physical
+    row count (``max + 1``)."""
 
     def __init__(
         self,
@@ -668,6 +986,8 @@ class EmbeddingBagCollection(nn.Module):
         is_weighted: bool = False,
         device: Optional[torch.device] = None,
         output_dtype: torch.dtype = torch.float32,
+        bounds_check: bool = False,
+        index_remapping: Optional[Dict[str, torch.Tensor]] = None,
     ) -> None:
         super().__init__()
         self._embedding_bag_configs = tables
@@ -677,13 +997,16 @@ class EmbeddingBagCollection(nn.Module):
         self._lengths_per_embedding = [t.embedding_dim for t in tables for _ in t.feature_names]
         poolings = {t.pooling for t in tables}
         assert len(poolings) <= 1, "uniform pooling per quant EBC group"
+        specs, remaps = _tbe_pruning_args(tables, index_remapping, "this quant EBC")
         self._tbe = QuantTableBatchedEmbeddingBags(
-            [(t.name, t.num_embeddings, t.embedding_dim) for t in tables],
+            specs,
             feature_table_map=[i for i, t in enumerate(tables) for _ in t.feature_names],
             pooling=next(iter(poolings)) if poolings else PoolingType.SUM,
             device=device,
             weight_dtypes=[quant_data_type(t.data_type) for t in tables],
             output_dtype=output_dtype,
+            bounds_check=bounds_check,
+            index_remapping=remaps,
         )
 
     @classmethod
@@ -693,29 +1016,45 @@ class EmbeddingBagCollection(nn.Module):
         output_dtype: torch.dtype = torch.float32,
         weight_dtype: DataType = DataType.INT8,
         per_table_weight_dtype: Optional[Dict[str, DataType]] = None,
+        bounds_check: bool = False,
+        index_remapping: Optional[Dict[str, torch.Tensor]] = None,
     ):
+        """``index_remapping`` may name tables of other modules (they are
+        ignored here). A named table's float rows are its logical rows, gathered
+        through the remap, or already its physical rows: the row count decides
+        (``_float_rows_for_remap``)."""
         tables = module.embedding_bag_configs()
         device = next(module.parameters()).device if any(True for _ in module.parameters()) else torch.device("cpu")
+        own = {t.name for t in tables}
+        index_remapping = {n: r for n, r in (index_remapping or {}).items() if n in own}
+        qtables = [
+            EmbeddingBagConfig(
+                num_embeddings=t.num_embeddings,
+                embedding_dim=t.embedding_dim,
+                name=t.name,
+                feature_names=list(t.feature_names),
+                pooling=t.pooling,
+                data_type=_resolve_weight_dtype(t.name, weight_dtype, per_table_weight_dtype),
+                num_embeddings_post_pruning=t.num_embeddings_post_pruning,
+            )
+            for t in tables
+        ]
+        weights = []
+        for t in tables:
+            w = module.embedding_bags[t.name].weight.detach()
+            if t.name in index_remapping:
+                w = _float_rows_for_remap(t.name, w, index_remapping[t.name])
+            weights.append(w)
         q = cls(
-            tables=[
-                EmbeddingBagConfig(
-                    num_embeddings=t.num_embeddings,
-                    embedding_dim=t.embedding_dim,
-                    name=t.name,
-                    feature_names=list(t.feature_names),
-                    pooling=t.pooling,
-                    data_type=_resolve_weight_dtype(
-                        t.name, weight_dtype, per_table_weight_dtype
-                    ),
-                )
-                for t in tables
-            ],
+            tables=_quant_configs_for_remap(qtables, index_remapping),
             is_weighted=module.is_weighted(),
             device=device,
             output_dtype=output_dtype,
+            bounds_check=bounds_check,
+            index_remapping=index_remapping or None,
         )
-        for i, t in enumerate(tables):
-            q._tbe.load_float_table(i, module.embedding_bags[t.name].weight.detach())
+        for i, w in enumerate(weights):
+            q._tbe.load_float_table(i, w)
         return q
 
     def embedding_bag_configs(self) -> List[EmbeddingBagConfig]:
@@ -761,6 +1100,8 @@ class EmbeddingCollection(nn.Module):
         tables: List[EmbeddingConfig],
         device: Optional[torch.device] = None,
         output_dtype: torch.dtype = torch.float32,
+        bounds_check: bool = False,
+        index_remapping: Optional[Dict[str, torch.Tensor]] = None,
     ) -> None:
         super().__init__()
         self._embedding_configs = tables
@@ -769,12 +1110,15 @@ class EmbeddingCollection(nn.Module):
         dims = {t.embedding_dim for t in tables}
         assert len(dims) <= 1
         self._dim = next(iter(dims)) if dims else 0
+        specs, remaps = _tbe_pruning_args(tables, index_remapping, "this quant EC")
         self._tbe = QuantTableBatchedEmbeddingBags(
-            [(t.name, t.num_embeddings, t.embedding_dim) for t in tables],
+            specs,
             feature_table_map=[i for i, t in enumerate(tables) for _ in t.feature_names],
             device=device,
             weight_dtypes=[quant_data_type(t.data_type) for t in tables],
             output_dtype=output_dtype,
+            bounds_check=bounds_check,
+            index_remapping=remaps,
         )
 
     @classmethod
@@ -784,7 +1128,10 @@ class EmbeddingCollection(nn.Module):
         output_dtype: torch.dtype = torch.float32,
         weight_dtype: DataType = DataType.INT8,
         per_table_weight_dtype: Optional[Dict[str, DataType]] = None,
+        bounds_check: bool = False,
+        index_remapping: Optional[Dict[str, torch.Tensor]] = None,
     ):
+        """``bounds_check`` / ``index_remapping``: as the quant EBC's ``from_float``."""
         tables = [
             dataclasses.replace(
                 t,
@@ -793,9 +1140,22 @@ class EmbeddingCollection(nn.Module):
             )
             for t in module.embedding_configs()
         ]
-        q = cls(tables=tables, output_dtype=output_dtype)
-        for i, t in enumerate(tables):
-            q._tbe.load_float_table(i, module.embeddings[t.name].weight.detach())
+        own = {t.name for t in tables}
+        index_remapping = {n: r for n, r in (index_remapping or {}).items() if n in own}
+        weights = []
+        for t in tables:
+            w = module.embeddings[t.name].weight.detach()
+            if t.name in index_remapping:
+                w = _float_rows_for_remap(t.name, w, index_remapping[t.name])
+            weights.append(w)
+        q = cls(
+            tables=_quant_configs_for_remap(tables, index_remapping),
+            output_dtype=output_dtype,
+            bounds_check=bounds_check,
+            index_remapping=index_remapping or None,
+        )
+        for i, w in enumerate(weights):
+            q._tbe.load_float_table(i, w)
         return q
 
     def embedding_configs(self) -> List[EmbeddingConfig]:
@@ -829,8 +1189,10 @@ class EmbeddingCollection(nn.Module):
         else:
             rows_l = []
             for f, t in enumerate(tbe._feature_table_map):
-                w = tbe.dequantized_table(t)
+                w = tbe._cpu_lookup_table(t)
                 idx = features.values()[int(offsets[f * B]) : int(offsets[(f + 1) * B])]
+                if tbe._checked:
+                    idx = tbe._map_ids_cpu(t, idx)  # -1 indexes the appended zero row
                 rows_l.append(w[idx])
             rows = torch.cat(rows_l, dim=0) if rows_l else torch.empty(0, self._dim)
             rows = tbe.to_output_dtype(rows)
