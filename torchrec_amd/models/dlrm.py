@@ -9,6 +9,7 @@ MFMA interaction kernel is the planned upgrade.
 
 from __future__ import annotations
 
+import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -118,7 +119,30 @@ class LowRankCrossNet(nn.Module):
             [nn.Parameter(torch.nn.init.zeros_(torch.empty(in_features))) for _ in range(num_layers)]
         )
 
+    def _fused_ok(self, input: torch.Tensor) -> bool:
+        """Fused MFMA kernels (ops.lowrank_cross): opt-in with
+        TREC_CROSSNET_FUSED=1, because at B=8192, N=3456, r=512 they measured
+        slower than the hipBLASLt chain below (docs/KERNELS.md). Taken only for
+        bf16 CUDA input inside the kernels' shape rules, gated on dtype and not
+        shape alone, so fp32/fp16 callers keep their precision;
+        TREC_CROSSNET_EAGER=1 always wins."""
+        if os.environ.get("TREC_CROSSNET_FUSED") != "1":
+            return False
+        if os.environ.get("TREC_CROSSNET_EAGER") == "1" or self._num_layers == 0:
+            return False
+        if not (input.is_cuda and input.dtype == torch.bfloat16 and input.dim() == 2):
+            return False
+        from torchrec_amd import ops
+
+        return ops.lowrank_cross_shape_ok(input.shape[1], self.V_kernels[0].shape[0])
+
     def forward(self, input: torch.Tensor) -> torch.Tensor:
+        if self._fused_ok(input):
+            from torchrec_amd import ops
+
+            return ops.lowrank_cross(
+                input, list(self.V_kernels), list(self.W_kernels), list(self.bias)
+            )
         x_0 = input
         x_l = x_0
         for layer in range(self._num_layers):

@@ -487,6 +487,101 @@ def fused_interaction(dense: torch.Tensor, sparse: torch.Tensor) -> torch.Tensor
     return _FusedInteraction.apply(dense, sparse)
 
 
+# ------------------------------------------------------------------------
+# fused DCN-v2 low-rank cross stack (csrc/cross_mfma.hip)
+# ------------------------------------------------------------------------
+
+
+def lowrank_cross_shape_ok(n_features: int, rank: int) -> bool:
+    """Shape rules of the fused cross kernels (bf16 operands assumed)."""
+    return n_features > 0 and n_features % 32 == 0 and rank % 32 == 0 and 32 <= rank <= 512
+
+
+def _cross_wgrad(g: torch.Tensor, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(g^T @ x, colsum(g)) over the batch: the hipBLASLt bias-grad epilogue
+    GEMM where the batch is a multiple of 8 rows and at least one k tile
+    deep, torch.matmul + the col_sum kernel otherwise."""
+    if g.shape[0] >= 64 and g.shape[0] % 8 == 0:
+        return torch.ops.trec_amd.lt_wgrad_bgrad(g, x)
+    return g.t() @ x, torch.ops.trec_amd.col_sum(g)
+
+
+class _LowRankCross(torch.autograd.Function):
+    """x_{l+1} = x_0 * (W_l (V_l x_l) + b_l) + x_l for the whole stack: one
+    forward and one backward-data kernel per layer; the weight gradients are
+    batch-deep GEMMs over the kernels' u = g * x_0 and dt = u W outputs."""
+
+    @staticmethod
+    def forward(ctx, x0, save_t, num_layers, *params):  # type: ignore[override]
+        L = num_layers
+        bf16 = torch.bfloat16
+        Vs = [p.to(bf16) for p in params[:L]]
+        Ws = [p.to(bf16) for p in params[L : 2 * L]]
+        bs = [p.float() for p in params[2 * L :]]
+        xs, ts = [x0], []
+        for l in range(L):
+            y, t = torch.ops.trec_amd.lowrank_cross_fwd(x0, xs[-1], Vs[l], Ws[l], bs[l], save_t)
+            xs.append(y)
+            ts.append(t)
+        if save_t:
+            ctx.save_for_backward(*xs[:L], *ts, *Vs, *Ws, *bs)
+        ctx.num_layers = L
+        ctx.param_dtypes = [p.dtype for p in params]
+        return xs[-1]
+
+    @staticmethod
+    def backward(ctx, grad):  # type: ignore[override]
+        L = ctx.num_layers
+        saved = ctx.saved_tensors
+        xs, ts = saved[:L], saved[L : 2 * L]
+        Vs, Ws, bs = saved[2 * L : 3 * L], saved[3 * L : 4 * L], saved[4 * L :]
+        x0 = xs[0]
+        g = grad.to(torch.bfloat16).contiguous()
+        dx0_acc = torch.zeros(x0.shape, dtype=torch.float32, device=x0.device)
+        dV: List[Optional[torch.Tensor]] = [None] * L
+        dW: List[Optional[torch.Tensor]] = [None] * L
+        db: List[Optional[torch.Tensor]] = [None] * L
+        for l in reversed(range(L)):
+            g, u, dt = torch.ops.trec_amd.lowrank_cross_bwd(
+                g, x0, xs[l], ts[l], Vs[l], Ws[l], bs[l], dx0_acc
+            )
+            dW[l], db[l] = _cross_wgrad(u, ts[l])
+            dV[l], _ = _cross_wgrad(dt, xs[l])
+        # layer 0's x_l is x_0: fold its dx_l into the fp32 sum, cast once
+        dx0 = (dx0_acc + g.float()).to(x0.dtype)
+        grads = [d.to(dt_) for d, dt_ in zip(dV + dW + db, ctx.param_dtypes)]
+        return (dx0, None, None, *grads)
+
+
+def lowrank_cross(
+    x0: torch.Tensor,
+    V_list: List[torch.Tensor],
+    W_list: List[torch.Tensor],
+    b_list: List[torch.Tensor],
+) -> torch.Tensor:
+    """DCN-v2 low-rank cross stack (reference: torchrec/modules/crossnet.py
+    LowRankCrossNet): x_{l+1} = x_0 * (W_l (V_l x_l) + b_l) + x_l with V_l
+    [r, N], W_l [N, r], b_l [N].
+
+    GPU: bf16 x0, N % 32 == 0, r % 32 == 0, 32 <= r <= 512; fp32 parameters
+    are cast to bf16 for the call (b is read as fp32) and get gradients in
+    their own dtype. CPU: the plain recurrence."""
+    if not x0.is_cuda:
+        x_l = x0
+        for V, W, b in zip(V_list, W_list, b_list):
+            x_l_v = torch.nn.functional.linear(x_l, V)
+            x_l_w = torch.nn.functional.linear(x_l_v, W)
+            x_l = x0 * (x_l_w + b) + x_l
+        return x_l
+    hip_ops()
+    L = len(V_list)
+    if L == 0:
+        return x0
+    params = [*V_list, *W_list, *b_list]
+    save_t = torch.is_grad_enabled() and (x0.requires_grad or any(p.requires_grad for p in params))
+    return _LowRankCross.apply(x0.contiguous(), save_t, L, *params)
+
+
 class _FusedBceWithLogits(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels):  # type: ignore[override]

@@ -179,6 +179,13 @@ std::tuple<at::Tensor, at::Tensor> interaction_backward(const at::Tensor& grad_o
                                                         const at::Tensor& dense,
                                                         const at::Tensor& sparse,
                                                         const at::Tensor& pair_col);
+// cross_mfma.hip
+std::tuple<at::Tensor, at::Tensor> lowrank_cross_fwd(const at::Tensor& x0, const at::Tensor& xl,
+                                                     const at::Tensor& V, const at::Tensor& W,
+                                                     const at::Tensor& b, bool save_t);
+std::tuple<at::Tensor, at::Tensor, at::Tensor> lowrank_cross_bwd(
+    const at::Tensor& g, const at::Tensor& x0, const at::Tensor& xl, const at::Tensor& t,
+    const at::Tensor& V, const at::Tensor& W, const at::Tensor& b, at::Tensor dx0_acc);
 
 }  // namespace trec_amd
 
@@ -316,6 +323,12 @@ TORCH_LIBRARY(trec_amd, m) {
   m.def(
       "interaction_backward(Tensor grad_out, Tensor dense, Tensor sparse, Tensor pair_col)"
       " -> (Tensor, Tensor)");
+  m.def(
+      "lowrank_cross_fwd(Tensor x0, Tensor xl, Tensor V, Tensor W, Tensor b, bool save_t)"
+      " -> (Tensor y, Tensor t)");
+  m.def(
+      "lowrank_cross_bwd(Tensor g, Tensor x0, Tensor xl, Tensor t, Tensor V, Tensor W, Tensor b,"
+      " Tensor(a!) dx0_acc) -> (Tensor dxl, Tensor u, Tensor dt)");
 }
 
 TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
@@ -369,6 +382,8 @@ TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
   m.impl("interaction_mfma_forward", trec_amd::interaction_mfma_forward);
   m.impl("interaction_mfma_backward", trec_amd::interaction_mfma_backward);
   m.impl("interaction_backward", trec_amd::interaction_backward);
+  m.impl("lowrank_cross_fwd", trec_amd::lowrank_cross_fwd);
+  m.impl("lowrank_cross_bwd", trec_amd::lowrank_cross_bwd);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
