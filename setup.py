@@ -24,6 +24,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "interaction.hip"),
         os.path.join(CSRC, "interaction_mfma.hip"),
         os.path.join(CSRC, "cross_mfma.hip"),
+        os.path.join(CSRC, "qcomm_codec.hip"),
         os.path.join(CSRC, "mlp_ops.hip"),
         os.path.join(CSRC, "lt_gemm.hip"),
         os.path.join(CSRC, "cache.hip"),

@@ -131,7 +131,8 @@ class _All2AllPooledWait(torch.autograd.Function):
         ctx.pg = pg
         B = meta.B
         if meta.codec is not None:
-            out = meta.codec.decode(out, B * sum(meta.dim_sum_per_rank))
+            # decode and rank-block paste in one step (one kernel for MXFP8/4)
+            return meta.codec.decode_pooled_blocks(out, B, meta.dim_sum_per_rank)
         blocks = []
         off = 0
         for d in meta.dim_sum_per_rank:
@@ -147,18 +148,19 @@ class _All2AllPooledWait(torch.autograd.Function):
         W = dist.get_world_size(pg)
         B, D_local = meta.B, meta.D_local
         # split cols back per rank, flatten blocks, a2a mirror
-        grads = []
-        off = 0
-        for d in meta.dim_sum_per_rank:
-            grads.append(grad_output[:, off : off + d].reshape(-1))
-            off += d
-        flat = torch.cat(grads)
         if meta.codec is not None:
-            flat = meta.codec.encode(flat)
+            # rank-block gather and encode in one step (one kernel for MXFP8/4)
+            flat = meta.codec.encode_pooled_blocks(grad_output, meta.dim_sum_per_rank)
             out = flat.new_empty(meta.codec.encoded_numel(W * B * D_local))
             in_splits = [meta.codec.encoded_numel(B * d) for d in meta.dim_sum_per_rank]
             out_splits = [meta.codec.encoded_numel(B * D_local)] * W
         else:
+            grads = []
+            off = 0
+            for d in meta.dim_sum_per_rank:
+                grads.append(grad_output[:, off : off + d].reshape(-1))
+                off += d
+            flat = torch.cat(grads)
             out = flat.new_empty(W * B * D_local)
             in_splits = [B * d for d in meta.dim_sum_per_rank]
             out_splits = [B * D_local] * W
@@ -182,6 +184,14 @@ def alltoall_pooled(
         assert codec.precision != CommType.INT8, (
             "INT8 comm needs per-block scales; use FP16/BF16/FP8 for a2a"
         )
+        g = getattr(codec, "group_size", 1)
+        bad = [d for d in (*dim_sum_per_rank, pooled.shape[1]) if d % g != 0]
+        if bad:
+            raise ValueError(
+                f"{codec.precision.value} comm quantizes groups of {g} values: every "
+                f"dim_sum_per_rank entry and D_local must be a multiple of {g}, got "
+                f"dim_sum_per_rank={list(dim_sum_per_rank)}, D_local={pooled.shape[1]}"
+            )
     """Async pooled-embedding a2a (reference comm_ops.py:508).
 
     ``pooled``: [W*B_local, D_local] laid out source-rank-major.

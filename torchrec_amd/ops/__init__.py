@@ -719,3 +719,91 @@ def keyed_jagged_index_select_dim1(
     )
     pl, pv, pw = permute_1d_sparse_data(sel, lengths, values, weights)
     return pv, pl, pw
+
+
+# ------------------------------------------------------------------------
+# OCP microscaling wire codec for the quantized a2a (csrc/qcomm_codec.hip)
+# ------------------------------------------------------------------------
+
+# groups of 32 values per workgroup tile of the HIP kernels (kMxTileGroups)
+QCOMM_MX_TILE_GROUPS = 256
+_MX_FMT_IDS = {"mxfp8": 0, "mxfp4": 1}
+_MX_COL_OFFS: dict = {}
+
+
+def _mx_col_off(block_dims: List[int], device: torch.device) -> torch.Tensor:
+    """Device int32 [n_blocks + 1] first column of every rank block."""
+    key = (tuple(block_dims), device)
+    if key not in _MX_COL_OFFS:
+        offs = [0]
+        for d in block_dims:
+            assert d % 32 == 0, f"MX slab blocks need widths % 32 == 0, got {list(block_dims)}"
+            offs.append(offs[-1] + d)
+        _MX_COL_OFFS[key] = torch.tensor(offs, dtype=torch.int32).to(device)
+    return _MX_COL_OFFS[key]
+
+
+def _mx_no_table(device: torch.device) -> torch.Tensor:
+    """Requires the extension; the empty column table selects flat mode."""
+    assert hip_ops().qcomm_mx_tile_groups == QCOMM_MX_TILE_GROUPS
+    return torch.empty(0, dtype=torch.int32, device=device)
+
+
+def qcomm_mx_encode(
+    x: torch.Tensor, fmt: str, block_dims: Optional[List[int]] = None
+) -> torch.Tensor:
+    """fp32 message -> int8 MXFP8 / MXFP4 wire (``fmt``: "mxfp8" | "mxfp4").
+
+    Flat (``block_dims`` None): ``x`` is the message. Slab: ``x`` is a
+    [B, sum(block_dims)] matrix and the message is the concatenation over r
+    of its flattened [B, block_dims[r]] column block.
+    """
+    if block_dims is not None:
+        assert x.dim() == 2 and x.shape[1] == sum(block_dims), (tuple(x.shape), block_dims)
+    if x.is_cuda:
+        no_table = _mx_no_table(x.device)
+        x = x.float()
+        if block_dims is None:
+            return torch.ops.trec_amd.qcomm_mx_encode(x.reshape(-1), _MX_FMT_IDS[fmt], no_table, 0)
+        return torch.ops.trec_amd.qcomm_mx_encode(
+            x, _MX_FMT_IDS[fmt], _mx_col_off(block_dims, x.device), x.shape[0]
+        )
+    from torchrec_amd.distributed import qcomm_codecs as qc
+
+    if block_dims is not None:
+        x = qc._gather_pooled_blocks(x, block_dims)
+    return qc.mx_encode_reference(x, fmt)
+
+
+def qcomm_mx_decode(
+    wire: torch.Tensor,
+    numel: int,
+    fmt: str,
+    block_dims: Optional[List[int]] = None,
+    B: Optional[int] = None,
+    out: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """int8 wire -> fp32: the flat [numel] message, or with ``block_dims``
+    and ``B`` the [B, sum(block_dims)] matrix whose column blocks it holds.
+    ``out`` (contiguous fp32 of that shape) is overwritten when given."""
+    if block_dims is not None:
+        assert B is not None and numel == B * sum(block_dims), (numel, B, block_dims)
+    shape = (numel,) if block_dims is None else (B, numel // max(B, 1))
+    assert out is None or tuple(out.shape) == shape, (tuple(out.shape), shape)
+    if wire.is_cuda:
+        no_table = _mx_no_table(wire.device)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=wire.device)
+        if block_dims is None:
+            torch.ops.trec_amd.qcomm_mx_decode(wire, out, _MX_FMT_IDS[fmt], no_table, 0)
+        else:
+            torch.ops.trec_amd.qcomm_mx_decode(
+                wire, out, _MX_FMT_IDS[fmt], _mx_col_off(block_dims, wire.device), B
+            )
+        return out
+    from torchrec_amd.distributed import qcomm_codecs as qc
+
+    res = qc.mx_decode_reference(wire, numel, fmt)
+    if block_dims is not None:
+        res = qc._paste_pooled_blocks(res, B, block_dims)
+    return res if out is None else out.copy_(res)

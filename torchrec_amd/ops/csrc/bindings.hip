@@ -186,6 +186,12 @@ std::tuple<at::Tensor, at::Tensor> lowrank_cross_fwd(const at::Tensor& x0, const
 std::tuple<at::Tensor, at::Tensor, at::Tensor> lowrank_cross_bwd(
     const at::Tensor& g, const at::Tensor& x0, const at::Tensor& xl, const at::Tensor& t,
     const at::Tensor& V, const at::Tensor& W, const at::Tensor& b, at::Tensor dx0_acc);
+// qcomm_codec.hip
+at::Tensor qcomm_mx_encode(const at::Tensor& src, int64_t fmt, const at::Tensor& col_off,
+                           int64_t B);
+void qcomm_mx_decode(const at::Tensor& wire, at::Tensor out, int64_t fmt,
+                     const at::Tensor& col_off, int64_t B);
+int64_t qcomm_mx_tile_groups();
 
 }  // namespace trec_amd
 
@@ -329,6 +335,8 @@ TORCH_LIBRARY(trec_amd, m) {
   m.def(
       "lowrank_cross_bwd(Tensor g, Tensor x0, Tensor xl, Tensor t, Tensor V, Tensor W, Tensor b,"
       " Tensor(a!) dx0_acc) -> (Tensor dxl, Tensor u, Tensor dt)");
+  m.def("qcomm_mx_encode(Tensor src, int fmt, Tensor col_off, int B) -> Tensor");
+  m.def("qcomm_mx_decode(Tensor wire, Tensor(a!) out, int fmt, Tensor col_off, int B) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
@@ -384,9 +392,12 @@ TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
   m.impl("interaction_backward", trec_amd::interaction_backward);
   m.impl("lowrank_cross_fwd", trec_amd::lowrank_cross_fwd);
   m.impl("lowrank_cross_bwd", trec_amd::lowrank_cross_bwd);
+  m.impl("qcomm_mx_encode", trec_amd::qcomm_mx_encode);
+  m.impl("qcomm_mx_decode", trec_amd::qcomm_mx_decode);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("loaded", []() { return true; });
   m.attr("__hip_arch__") = "gfx950";
+  m.attr("qcomm_mx_tile_groups") = trec_amd::qcomm_mx_tile_groups();
 }
