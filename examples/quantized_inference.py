@@ -4,6 +4,8 @@ default) -> shard for inference -> serve through the native batching runtime.
 Run (1 GPU):  python examples/quantized_inference.py [--weight-dtype FP8]
 ``--weight-dtype`` is INT8, INT4, INT2 or FP8 (e4m3fn codes with a rowwise
 scale: the bytes of INT8, a relative instead of an absolute error).
+``--dense-format mxfp8`` also swaps the dense and over arch MLPs for their
+MXFP8 forms (``inference.modules.quantize_dense``).
 CPU works too (reference dequant path).
 """
 
@@ -28,6 +30,8 @@ from torchrec_amd.sparse.jagged_tensor import KeyedJaggedTensor
 def main() -> None:
     parser = argparse.ArgumentParser()
     parser.add_argument("--weight-dtype", default="INT8", choices=["INT8", "INT4", "INT2", "FP8"])
+    parser.add_argument("--dense-format", default=None, choices=["mxfp8"],
+                        help="also serve the dense MLPs quantized (MXFP8 weights and activations)")
     args = parser.parse_args()
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     keys = [f"cat_{i}" for i in range(4)]
@@ -52,7 +56,8 @@ def main() -> None:
     # device instead of being read (index_remapping={table: remap} would also
     # serve pruned tables at their pruned size)
     qmodel = quantize_inference_model(
-        model, weight_dtype=DataType[args.weight_dtype], bounds_check=True
+        model, weight_dtype=DataType[args.weight_dtype], bounds_check=True,
+        dense_format=args.dense_format,
     )
     qmodel = qmodel.to(device)
 

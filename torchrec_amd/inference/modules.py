@@ -31,6 +31,8 @@ def quantize_inference_model(
     per_table_weight_dtype: Optional[Dict[str, DataType]] = None,
     bounds_check: bool = False,
     index_remapping: Optional[Dict[str, torch.Tensor]] = None,
+    dense_format: Optional[str] = None,
+    dense_output_dtype: torch.dtype = torch.float32,
 ) -> nn.Module:
     """Swap float embedding modules for rowwise-quantized ones in-place
     (reference inference/modules.py:372). Tables are packed at
@@ -41,7 +43,11 @@ def quantize_inference_model(
     its tables instead of reading them; ``index_remapping`` (table name ->
     int32/int64 ``[num_embeddings]`` tensor of physical rows, -1 = pruned)
     serves the named tables pruned. Both are
-    ``QuantTableBatchedEmbeddingBags``'s arguments, by table name."""
+    ``QuantTableBatchedEmbeddingBags``'s arguments, by table name.
+
+    ``dense_format="mxfp8"`` also swaps the dense MLPs (``quantize_dense``
+    with ``output_dtype=dense_output_dtype``); the default leaves them as they
+    are. ``output_dtype`` is the embeddings' alone: the two are not coupled."""
     mapping = quantization_mapping or {
         FloatEBC: QuantEBC,
         FloatEC: QuantEC,
@@ -66,6 +72,67 @@ def quantize_inference_model(
                 _swap(child)
 
     _swap(model)
+    if dense_format is not None:
+        quantize_dense(model, weight_format=dense_format, output_dtype=dense_output_dtype)
+    return model
+
+
+def quantize_dense(
+    model: nn.Module,
+    weight_format: str = "mxfp8",
+    output_dtype: torch.dtype = torch.float32,
+    skip=(),
+) -> nn.Module:
+    """Swap every ``MLP`` / ``Perceptron`` of ``model`` for its MXFP8 form
+    (``quant.mlp``), in place, and return the model. The counterpart of the
+    reference's ``quantize_dense`` (inference/modules.py), which casts the
+    dense modules to fp16. ``skip`` holds module names (as in
+    ``named_modules``) that stay float, with everything below them.
+
+    ``output_dtype`` (fp32 or bf16) is what the layers inside a swapped
+    ``MLP`` hand to each other. A swapped module's own result keeps the dtype
+    of the float module it replaces (its weight dtype, fp32 or bf16; anything
+    else raises here), so the float modules around it, such as the
+    interaction or the over arch's final ``nn.Linear``, see what they saw
+    before. A lone ``Perceptron`` has no layer after it, so ``output_dtype``
+    does not touch it.
+
+    Only children whose type is exactly ``MLP`` or ``Perceptron`` are swapped:
+    a subclass keeps its float shell (the ``Perceptron``s inside a subclassed
+    ``MLP`` are still swapped one by one), and so does a ``model`` that is
+    itself an ``MLP``."""
+    if weight_format != "mxfp8":
+        raise ValueError(f"quantize_dense: unknown weight_format {weight_format!r} (only 'mxfp8')")
+    if output_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"quantize_dense: output_dtype must be fp32 or bf16, got {output_dtype}")
+    from torchrec_amd.modules.mlp import MLP, Perceptron
+    from torchrec_amd.quant.mlp import QuantMLP, QuantPerceptron
+
+    skip = set(skip)
+
+    def _float_dtype(path: str, child: nn.Module) -> torch.dtype:
+        dtype = next((p.dtype for p in child.parameters()), torch.float32)
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"quantize_dense: {path} is {dtype}; only fp32 and bf16 modules")
+        return dtype
+
+    def _swap(parent: nn.Module, prefix: str) -> None:
+        for name, child in list(parent.named_children()):
+            path = prefix + name
+            if path in skip:
+                continue
+            if type(child) is MLP:
+                q = QuantMLP.from_float(
+                    child, output_dtype=output_dtype, result_dtype=_float_dtype(path, child)
+                )
+                setattr(parent, name, q)
+            elif type(child) is Perceptron:
+                q = QuantPerceptron.from_float(child, output_dtype=_float_dtype(path, child))
+                setattr(parent, name, q)
+            else:
+                _swap(child, path + ".")
+
+    _swap(model, "")
     return model
 
 

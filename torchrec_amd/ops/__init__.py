@@ -807,3 +807,86 @@ def qcomm_mx_decode(
     if block_dims is not None:
         res = qc._paste_pooled_blocks(res, B, block_dims)
     return res if out is None else out.copy_(res)
+
+
+# ------------------------------------------------------------------------
+# MXFP8 linear layer for serving (csrc/mx_linear.hip)
+# ------------------------------------------------------------------------
+
+MX_LINEAR_K_STEP = 128  # codes are padded to a multiple of this many k
+# widest workgroup column tile of the GEMM instantiations (kBigBN); checked
+# against the extension's own value on every GPU call
+MX_LINEAR_WIDEST_TILE = 128
+_MX_OUT_DTYPES = {torch.float32: 0, torch.bfloat16: 1}
+
+
+def _mx_linear_ext() -> None:
+    """Requires the extension and that its tiles are the ones stated here."""
+    assert hip_ops().mx_linear_widest_tile == MX_LINEAR_WIDEST_TILE
+
+
+def _mx_rows(t: torch.Tensor, width: int) -> torch.Tensor:
+    """fp32 [R, width] with the rows zero-padded from t's width."""
+    out = torch.zeros(t.shape[0], width, dtype=torch.float32, device=t.device)
+    out[:, : t.shape[1]] = t.float()
+    return out
+
+
+def mx_linear_pack_weight(weight: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """W [N, K] -> (codes uint8 [N, Kp], scales uint8 [N, Kp / 32]): MXFP8
+    groups of 32 consecutive k of each row, Kp = K rounded up to 128, a
+    ragged last group quantized as if padded with zeros, padding groups zero."""
+    assert weight.dim() == 2 and weight.shape[0] >= 1 and weight.shape[1] >= 1, tuple(weight.shape)
+    if weight.is_cuda:
+        _mx_linear_ext()
+        return torch.ops.trec_amd.mx_linear_pack_weight(weight.detach().float())
+    from torchrec_amd.distributed import qcomm_codecs as qc
+
+    N, K = weight.shape
+    Kp = -(-K // MX_LINEAR_K_STEP) * MX_LINEAR_K_STEP
+    wire = qc.mx_encode_reference(_mx_rows(weight.detach(), Kp).reshape(-1), "mxfp8")
+    wire = wire.view(torch.uint8).reshape(N, Kp // 32, 33)
+    return wire[:, :, :32].reshape(N, Kp).contiguous(), wire[:, :, 32].contiguous()
+
+
+def mx_linear(
+    x: torch.Tensor,
+    codes: torch.Tensor,
+    scales: torch.Tensor,
+    bias: Optional[torch.Tensor],
+    in_features: int,
+    relu: bool = False,
+    output_dtype: torch.dtype = torch.float32,
+) -> torch.Tensor:
+    """y = act(Qx(x) Qw(W)^T + b) with both operands in MXFP8 (groups of 32
+    consecutive k per row), fp32 accumulation, bias and ReLU on the fp32 sum,
+    one rounding to ``output_dtype`` (fp32 or bf16). ``x`` is [..., K] fp32 or
+    bf16; ``codes`` / ``scales`` come from ``mx_linear_pack_weight``.
+
+    GPU: the block-scaled MFMA kernel. CPU: the same contract in plain
+    PyTorch (reference quantize / dequantize, fp32 matmul)."""
+    assert output_dtype in _MX_OUT_DTYPES, f"mx_linear: output_dtype {output_dtype}"
+    K = in_features
+    assert x.shape[-1] == K, (tuple(x.shape), K)
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, K)
+    if x.is_cuda:
+        _mx_linear_ext()
+        y = torch.ops.trec_amd.mx_linear_fwd(
+            x2, codes, scales, bias, K, relu, _MX_OUT_DTYPES[output_dtype]
+        )
+        return y.reshape(*lead, codes.shape[0])
+    from torchrec_amd.distributed import qcomm_codecs as qc
+
+    N, Kp = codes.shape
+    xq = qc.mx_decode_reference(
+        qc.mx_encode_reference(_mx_rows(x2, Kp).reshape(-1), "mxfp8"), x2.shape[0] * Kp, "mxfp8"
+    ).reshape(-1, Kp)
+    wire = torch.cat([codes.reshape(N, Kp // 32, 32), scales.reshape(N, Kp // 32, 1)], dim=2)
+    wq = qc.mx_decode_reference(wire.reshape(-1).view(torch.int8), N * Kp, "mxfp8").reshape(N, Kp)
+    y = xq @ wq.t()
+    if bias is not None:
+        y = y + bias.float()
+    if relu:
+        y = torch.relu(y)
+    return y.to(output_dtype).reshape(*lead, N)

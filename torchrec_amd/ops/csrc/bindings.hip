@@ -192,6 +192,12 @@ at::Tensor qcomm_mx_encode(const at::Tensor& src, int64_t fmt, const at::Tensor&
 void qcomm_mx_decode(const at::Tensor& wire, at::Tensor out, int64_t fmt,
                      const at::Tensor& col_off, int64_t B);
 int64_t qcomm_mx_tile_groups();
+// mx_linear.hip
+std::tuple<at::Tensor, at::Tensor> mx_linear_pack_weight(const at::Tensor& W);
+at::Tensor mx_linear_fwd(const at::Tensor& x, const at::Tensor& codes, const at::Tensor& scales,
+                         const c10::optional<at::Tensor>& bias, int64_t K, bool relu,
+                         int64_t output_dtype);
+int64_t mx_linear_widest_tile();
 
 }  // namespace trec_amd
 
@@ -337,6 +343,10 @@ TORCH_LIBRARY(trec_amd, m) {
       " Tensor(a!) dx0_acc) -> (Tensor dxl, Tensor u, Tensor dt)");
   m.def("qcomm_mx_encode(Tensor src, int fmt, Tensor col_off, int B) -> Tensor");
   m.def("qcomm_mx_decode(Tensor wire, Tensor(a!) out, int fmt, Tensor col_off, int B) -> ()");
+  m.def("mx_linear_pack_weight(Tensor W) -> (Tensor codes, Tensor scales)");
+  m.def(
+      "mx_linear_fwd(Tensor x, Tensor codes, Tensor scales, Tensor? bias, int K, bool relu,"
+      " int output_dtype=0) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
@@ -394,10 +404,13 @@ TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
   m.impl("lowrank_cross_bwd", trec_amd::lowrank_cross_bwd);
   m.impl("qcomm_mx_encode", trec_amd::qcomm_mx_encode);
   m.impl("qcomm_mx_decode", trec_amd::qcomm_mx_decode);
+  m.impl("mx_linear_pack_weight", trec_amd::mx_linear_pack_weight);
+  m.impl("mx_linear_fwd", trec_amd::mx_linear_fwd);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("loaded", []() { return true; });
   m.attr("__hip_arch__") = "gfx950";
   m.attr("qcomm_mx_tile_groups") = trec_amd::qcomm_mx_tile_groups();
+  m.attr("mx_linear_widest_tile") = trec_amd::mx_linear_widest_tile();
 }

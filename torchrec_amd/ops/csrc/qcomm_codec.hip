@@ -42,6 +42,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
 #include "common.h"
+#include "mx_quant.h"
 
 namespace trec_amd {
 
@@ -52,21 +53,6 @@ constexpr int kMxThreads = 256;
 constexpr int kMxLanesPerGroup = 8;  // one float4 each
 constexpr int kMxGroupsPerPass = kMxThreads / kMxLanesPerGroup;
 constexpr int kMxPasses = kMxTileGroups / kMxGroupsPerPass;
-constexpr int kFmtMxfp8 = 0;
-constexpr int kFmtMxfp4 = 1;
-
-template <int FMT>
-struct MxFmt;
-template <>
-struct MxFmt<kFmtMxfp8> {
-  static constexpr int kGroupBytes = 33, kScaleAt = 32, kEmax = 8;
-  static constexpr unsigned kMantMax = 0x600000u;  // 448 = 1.75 * 2^8
-};
-template <>
-struct MxFmt<kFmtMxfp4> {
-  static constexpr int kGroupBytes = 17, kScaleAt = 16, kEmax = 2;
-  static constexpr unsigned kMantMax = 0x400000u;  // 6 = 1.5 * 2^2
-};
 
 // Slab addressing: col_off[r] is the first column of block r (col_off[n] is
 // sum_D), so block r starts at logical group B * col_off[r] / 32.
@@ -79,7 +65,8 @@ struct MxSlab {
 
 // Device code of this file is built without the packed fp32 VALU forms (see
 // cross_mfma.hip): everything the kernels call is defined between the push
-// and the pop, with builtins rather than header helpers.
+// and the pop or in mx_quant.h (built the same way; shared with
+// mx_linear.hip), with builtins rather than header helpers.
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
@@ -95,23 +82,6 @@ __device__ __forceinline__ void msync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-__device__ __forceinline__ unsigned mumax(unsigned a, unsigned b) { return a > b ? a : b; }
-__device__ __forceinline__ unsigned mbits(float v) { return __builtin_bit_cast(unsigned, v); }
-
-// 2^e for e in [-127, 127]; 2^-127 is the fp32 subnormal 0x00400000.
-__device__ __forceinline__ float mpow2(int e) {
-  return __builtin_bit_cast(float, e > -127 ? static_cast<unsigned>(e + 127) << 23 : 0x00400000u);
-}
-
-// max over the eight lanes of a group: lane^1, lane^2 by quad permutes, then
-// the other quad by a mirror of the half row (every lane of a quad already
-// holds the quad's max).
-__device__ __forceinline__ unsigned group8_umax(unsigned a) {
-  a = mumax(a, static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(a), 0xB1, 0xF, 0xF, false)));
-  a = mumax(a, static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(a), 0x4E, 0xF, 0xF, false)));
-  a = mumax(a, static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(a), 0x141, 0xF, 0xF, false)));
-  return a;
 }
 
 // Element offset of logical group g. Flat: g * 32. Slab: row and column of
@@ -183,30 +153,15 @@ __global__ __launch_bounds__(kMxThreads) void qcomm_mx_encode_kernel(
     const int gl = p * kMxGroupsPerPass + gsub;
     const unsigned b0 = mbits(v[p][0]), b1 = mbits(v[p][1]), b2 = mbits(v[p][2]),
                    b3 = mbits(v[p][3]);
-    const unsigned a = group8_umax(mumax(mumax(b0 & 0x7FFFFFFFu, b1 & 0x7FFFFFFFu),
-                                         mumax(b2 & 0x7FFFFFFFu, b3 & 0x7FFFFFFFu)));
-    const int ex = static_cast<int>(a >> 23);
-    const bool nonfinite = ex == 255;
-    const bool special = nonfinite || a == 0u;
-    int E = ex - 127 - F::kEmax + ((a & 0x7FFFFFu) > F::kMantMax ? 1 : 0);
-    E = E < -127 ? -127 : (E > 127 ? 127 : E);
-    const unsigned scale_byte = nonfinite ? 0xFFu : (a == 0u ? 0u : static_cast<unsigned>(E + 127));
-    const float inv = mpow2(-E);
+    const MxScale sc = mx_scale_of<F::kEmax, F::kMantMax>(group8_umax(mx_amax4(b0, b1, b2, b3)));
+    const bool special = sc.special;
+    const unsigned scale_byte = sc.byte;
+    const float inv = mpow2(-sc.E);
     if (gl < ng) {
       uint8_t* gp = img + gl * F::kGroupBytes;
       if constexpr (FMT == kFmtMxfp8) {
-        // the clamp acts only where E was clamped; the convert rounds to
-        // nearest even and the sign bit is taken from x itself
-        int w = 0;
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v[p][0] * inv, -448.f, 448.f),
-                                            __builtin_amdgcn_fmed3f(v[p][1] * inv, -448.f, 448.f),
-                                            w, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v[p][2] * inv, -448.f, 448.f),
-                                            __builtin_amdgcn_fmed3f(v[p][3] * inv, -448.f, 448.f),
-                                            w, true);
-        const unsigned signs = ((b0 >> 31) << 7) | ((b1 >> 31) << 15) | ((b2 >> 31) << 23) |
-                               ((b3 >> 31) << 31);
-        const unsigned codes = (static_cast<unsigned>(w) & 0x7F7F7F7Fu) | signs;
+        const unsigned codes =
+            mx_fp8_pack4(v[p][0], v[p][1], v[p][2], v[p][3], inv, b0, b1, b2, b3);
         *reinterpret_cast<mu32_u*>(gp + 4 * j) = special ? 0u : codes;
       } else {
         // scaled convert with a unit scale: the multiply above already

@@ -1,0 +1,102 @@
+"""MXFP8 dense layers for serving: the quantized forms of ``modules.mlp``'s
+Perceptron / MLP (the reference's ``quantize_dense`` only casts to fp16).
+
+A layer holds its weight as MXFP8 codes and E8M0 scale bytes (groups of 32
+consecutive input features per output row, ``ops.mx_linear_pack_weight``) and
+runs ``ops.mx_linear``: the activations are quantized the same way inside the
+GEMM kernel, products and sums are fp32, and bias and ReLU ride the kernel's
+epilogue. Inference only."""
+
+from __future__ import annotations
+
+from typing import Callable, Optional, Union
+
+import torch
+import torch.nn as nn
+
+from torchrec_amd import ops
+from torchrec_amd.modules.mlp import MLP, Perceptron
+
+_OUTPUT_DTYPES = (torch.float32, torch.bfloat16)
+
+
+class QuantPerceptron(nn.Module):
+    """``activation(mx_linear(x))``. ReLU (``torch.relu`` / ``nn.ReLU``) and
+    identity ride the kernel; any other activation is applied by torch to the
+    kernel's un-activated output."""
+
+    def __init__(
+        self,
+        in_size: int,
+        codes: torch.Tensor,
+        scales: torch.Tensor,
+        bias: Optional[torch.Tensor],
+        activation: Union[Callable[[torch.Tensor], torch.Tensor], nn.Module] = torch.relu,
+        output_dtype: torch.dtype = torch.float32,
+    ) -> None:
+        super().__init__()
+        assert output_dtype in _OUTPUT_DTYPES, f"output_dtype must be fp32 or bf16, got {output_dtype}"
+        self._in_size = in_size
+        self._out_size = codes.shape[0]
+        self._output_dtype = output_dtype
+        self._activation_fn = activation
+        self._relu = activation is torch.relu or isinstance(activation, nn.ReLU)
+        self._identity = activation is None or isinstance(activation, nn.Identity)
+        self.register_buffer("codes", codes)
+        self.register_buffer("scales", scales)
+        self.register_buffer("bias", bias)
+
+    @classmethod
+    def from_float(
+        cls, module: Perceptron, output_dtype: torch.dtype = torch.float32
+    ) -> "QuantPerceptron":
+        linear = module._linear
+        codes, scales = ops.mx_linear_pack_weight(linear.weight)
+        bias = None if linear.bias is None else linear.bias.detach().float().clone()
+        return cls(module._in_size, codes, scales, bias, module._activation_fn, output_dtype)
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        if torch.is_grad_enabled() and input.requires_grad:
+            raise RuntimeError("QuantPerceptron is inference-only: its input requires grad")
+        y = ops.mx_linear(
+            input, self.codes, self.scales, self.bias, self._in_size,
+            relu=self._relu, output_dtype=self._output_dtype,
+        )
+        return y if self._relu or self._identity else self._activation_fn(y)
+
+
+class QuantMLP(nn.Module):
+    """Stack of QuantPerceptrons. Every layer, the intermediate ones too,
+    emits ``output_dtype``, unless ``result_dtype`` names another dtype for
+    the last layer (what ``quantize_dense`` uses to hand the stack's result
+    to float neighbours in their own dtype while the layers between stay
+    bf16)."""
+
+    def __init__(self, layers: nn.Sequential, in_size: int, out_size: int) -> None:
+        super().__init__()
+        self._mlp = layers
+        self._in_size = in_size
+        self._out_size = out_size
+
+    @classmethod
+    def from_float(
+        cls,
+        module: MLP,
+        output_dtype: torch.dtype = torch.float32,
+        result_dtype: Optional[torch.dtype] = None,
+    ) -> "QuantMLP":
+        last = len(module._mlp) - 1
+        layers = nn.Sequential(
+            *[
+                QuantPerceptron.from_float(
+                    p, output_dtype=(result_dtype or output_dtype) if i == last else output_dtype
+                )
+                for i, p in enumerate(module._mlp)
+            ]
+        )
+        return cls(layers, module._in_size, module._out_size)
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        if torch.is_grad_enabled() and input.requires_grad:
+            raise RuntimeError("QuantMLP is inference-only: its input requires grad")
+        return self._mlp(input)
