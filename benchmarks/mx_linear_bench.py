@@ -9,7 +9,9 @@ size M and per Perceptron layer, and for each arch as a whole chain:
   fp32   relu(linear) under inference_mode, what an unquantized model serves
   bf16   the same with bf16 weights and activations
   mxfp8  ops.mx_linear on packed weights, fp32 in and out (``mxfp8_bf16``:
-         bf16 between the layers of a chain; bf16 in and out for one layer)
+         bf16 between the layers of a chain; bf16 in and out for one layer;
+         ``mxfp8_act``: the MXFP8 codes and scales themselves between the
+         layers of a chain, in and out for one layer)
 The mx chains are what quantize_dense serves: the last Perceptron of an arch
 returns fp32 and the over arch's final nn.Linear stays an fp32 linear, which
 also keeps its fp32 weight bytes.
@@ -120,12 +122,30 @@ def _paths(layers, M, as_served=True):
             return h
         return run
 
+    # activation_format="mxfp8": the quantized layers hand each other the
+    # MXFP8 pair. Served, the first reads fp32 and the last returns fp32; a
+    # layer timed on its own reads a pair (x packed like a weight) and emits one.
+    xq = ops.MxActivation(*ops.mx_linear_pack_weight(x), layers[0][0])
+
+    def mx_act():
+        def run():
+            h = x if as_served else xq
+            for i, ((k, _, relu, quant), (c, s), w, b) in enumerate(zip(layers, packed, ws, bs)):
+                if quant:
+                    h = ops.mx_linear(h, c, s, b, k, relu=relu,
+                                      output_format=None if i == last_q else "mxfp8")
+                else:
+                    h = torch.nn.functional.linear(h, w, b)
+            return h
+        return run
+
     return {
         "fp32": eager(x, ws, bs),
         "bf16": eager(xh, wh, bh),
         "mxfp8": mx(x, torch.float32),
         # served, the float neighbours hand the first layer fp32
         "mxfp8_bf16": mx(x if as_served else xh, torch.bfloat16),
+        "mxfp8_act": mx_act(),
     }
 
 

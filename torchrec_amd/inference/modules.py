@@ -33,6 +33,7 @@ def quantize_inference_model(
     index_remapping: Optional[Dict[str, torch.Tensor]] = None,
     dense_format: Optional[str] = None,
     dense_output_dtype: torch.dtype = torch.float32,
+    dense_activation_format: Optional[str] = None,
 ) -> nn.Module:
     """Swap float embedding modules for rowwise-quantized ones in-place
     (reference inference/modules.py:372). Tables are packed at
@@ -47,7 +48,8 @@ def quantize_inference_model(
 
     ``dense_format="mxfp8"`` also swaps the dense MLPs (``quantize_dense``
     with ``output_dtype=dense_output_dtype``); the default leaves them as they
-    are. ``output_dtype`` is the embeddings' alone: the two are not coupled."""
+    are. ``output_dtype`` is the embeddings' alone: the two are not coupled.
+    ``dense_activation_format`` is ``quantize_dense``'s ``activation_format``."""
     mapping = quantization_mapping or {
         FloatEBC: QuantEBC,
         FloatEC: QuantEC,
@@ -73,7 +75,8 @@ def quantize_inference_model(
 
     _swap(model)
     if dense_format is not None:
-        quantize_dense(model, weight_format=dense_format, output_dtype=dense_output_dtype)
+        quantize_dense(model, weight_format=dense_format, output_dtype=dense_output_dtype,
+                       activation_format=dense_activation_format)
     return model
 
 
@@ -82,6 +85,7 @@ def quantize_dense(
     weight_format: str = "mxfp8",
     output_dtype: torch.dtype = torch.float32,
     skip=(),
+    activation_format: Optional[str] = None,
 ) -> nn.Module:
     """Swap every ``MLP`` / ``Perceptron`` of ``model`` for its MXFP8 form
     (``quant.mlp``), in place, and return the model. The counterpart of the
@@ -97,6 +101,12 @@ def quantize_dense(
     before. A lone ``Perceptron`` has no layer after it, so ``output_dtype``
     does not touch it.
 
+    ``activation_format="mxfp8"`` makes the layers inside a swapped ``MLP``
+    hand each other the MXFP8 codes and scales themselves where the layer's
+    activation rides the kernel (``QuantMLP``), instead of ``output_dtype``
+    tensors the next layer quantizes again. A lone ``Perceptron`` has no
+    neighbour to hand to and ignores it.
+
     Only children whose type is exactly ``MLP`` or ``Perceptron`` are swapped:
     a subclass keeps its float shell (the ``Perceptron``s inside a subclassed
     ``MLP`` are still swapped one by one), and so does a ``model`` that is
@@ -105,6 +115,9 @@ def quantize_dense(
         raise ValueError(f"quantize_dense: unknown weight_format {weight_format!r} (only 'mxfp8')")
     if output_dtype not in (torch.float32, torch.bfloat16):
         raise ValueError(f"quantize_dense: output_dtype must be fp32 or bf16, got {output_dtype}")
+    if activation_format not in (None, "mxfp8"):
+        raise ValueError(
+            f"quantize_dense: unknown activation_format {activation_format!r} (only 'mxfp8')")
     from torchrec_amd.modules.mlp import MLP, Perceptron
     from torchrec_amd.quant.mlp import QuantMLP, QuantPerceptron
 
@@ -123,7 +136,8 @@ def quantize_dense(
                 continue
             if type(child) is MLP:
                 q = QuantMLP.from_float(
-                    child, output_dtype=output_dtype, result_dtype=_float_dtype(path, child)
+                    child, output_dtype=output_dtype, result_dtype=_float_dtype(path, child),
+                    activation_format=activation_format,
                 )
                 setattr(parent, name, q)
             elif type(child) is Perceptron:

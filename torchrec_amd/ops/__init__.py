@@ -14,7 +14,7 @@ op surface (reference call sites cited per-op below).
 from __future__ import annotations
 
 import os
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple, Union
 
 import torch
 
@@ -818,6 +818,20 @@ MX_LINEAR_K_STEP = 128  # codes are padded to a multiple of this many k
 # against the extension's own value on every GPU call
 MX_LINEAR_WIDEST_TILE = 128
 _MX_OUT_DTYPES = {torch.float32: 0, torch.bfloat16: 1}
+_MX_OUT_MXFP8 = 2  # the kernel's output-format code after the two dtypes
+
+
+class MxActivation(NamedTuple):
+    """An activation of ``features`` columns handed from one ``mx_linear`` to
+    the next in MXFP8, in the layout ``mx_linear_pack_weight`` gives a weight:
+    ``codes`` uint8 [M, Kp] (Kp = features rounded up to 128), ``scales`` uint8
+    [M, Kp / 32], groups of 32 consecutive features of a row, a ragged last
+    group quantized as if padded with zeros, padding groups zero codes with
+    scale byte 0, a group holding NaN or Inf zero codes with scale 0xFF."""
+
+    codes: torch.Tensor
+    scales: torch.Tensor
+    features: int
 
 
 def _mx_linear_ext() -> None:
@@ -845,48 +859,88 @@ def mx_linear_pack_weight(weight: torch.Tensor) -> Tuple[torch.Tensor, torch.Ten
     N, K = weight.shape
     Kp = -(-K // MX_LINEAR_K_STEP) * MX_LINEAR_K_STEP
     wire = qc.mx_encode_reference(_mx_rows(weight.detach(), Kp).reshape(-1), "mxfp8")
-    wire = wire.view(torch.uint8).reshape(N, Kp // 32, 33)
-    return wire[:, :, :32].reshape(N, Kp).contiguous(), wire[:, :, 32].contiguous()
+    return _mx_split(wire, N, Kp)
+
+
+def _mx_split(wire: torch.Tensor, rows: int, width: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Reference wire of [rows, width] values -> (codes [rows, width], scales [rows, width / 32])."""
+    wire = wire.view(torch.uint8).reshape(rows, width // 32, 33)
+    return wire[:, :, :32].reshape(rows, width).contiguous(), wire[:, :, 32].contiguous()
+
+
+def _mx_dequant(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """(codes [R, W], scales [R, W / 32]) -> fp32 [R, W] through the reference codec."""
+    R, W = codes.shape
+    wire = torch.cat([codes.reshape(R, W // 32, 32), scales.reshape(R, W // 32, 1)], dim=2)
+    from torchrec_amd.distributed import qcomm_codecs as qc
+
+    return qc.mx_decode_reference(wire.reshape(-1).view(torch.int8), R * W, "mxfp8").reshape(R, W)
 
 
 def mx_linear(
-    x: torch.Tensor,
+    x: Union[torch.Tensor, MxActivation],
     codes: torch.Tensor,
     scales: torch.Tensor,
     bias: Optional[torch.Tensor],
     in_features: int,
     relu: bool = False,
     output_dtype: torch.dtype = torch.float32,
-) -> torch.Tensor:
+    output_format: Optional[str] = None,
+) -> Union[torch.Tensor, MxActivation]:
     """y = act(Qx(x) Qw(W)^T + b) with both operands in MXFP8 (groups of 32
     consecutive k per row), fp32 accumulation, bias and ReLU on the fp32 sum,
     one rounding to ``output_dtype`` (fp32 or bf16). ``x`` is [..., K] fp32 or
     bf16; ``codes`` / ``scales`` come from ``mx_linear_pack_weight``.
 
+    ``x`` may instead be the ``MxActivation`` an earlier call returned: its
+    codes and scales are the operand as they stand and nothing is quantized.
+    ``output_format="mxfp8"`` returns one: the rounding is then the MXFP8
+    quantization of groups of 32 output columns, and ``output_dtype`` is not
+    used. The pair is 2-D; leading dimensions are the caller's.
+
     GPU: the block-scaled MFMA kernel. CPU: the same contract in plain
     PyTorch (reference quantize / dequantize, fp32 matmul)."""
     assert output_dtype in _MX_OUT_DTYPES, f"mx_linear: output_dtype {output_dtype}"
+    assert output_format in (None, "mxfp8"), f"mx_linear: output_format {output_format!r}"
     K = in_features
-    assert x.shape[-1] == K, (tuple(x.shape), K)
-    lead = x.shape[:-1]
-    x2 = x.reshape(-1, K)
-    if x.is_cuda:
+    N, Kp = codes.shape
+    mx_in, mx_out = isinstance(x, MxActivation), output_format == "mxfp8"
+    if mx_in:
+        assert x.features == K and x.codes.dim() == 2 and x.codes.shape[1] == Kp, (
+            x.features, tuple(x.codes.shape), K)
+        lead, x2 = x.codes.shape[:1], x.codes
+    else:
+        assert x.shape[-1] == K, (tuple(x.shape), K)
+        lead = x.shape[:-1]
+        x2 = x.reshape(-1, K)
+        assert not mx_out or x.dim() == 2, "mx_linear: an MXFP8 result is 2-D, flatten x first"
+    if x2.is_cuda:
         _mx_linear_ext()
-        y = torch.ops.trec_amd.mx_linear_fwd(
-            x2, codes, scales, bias, K, relu, _MX_OUT_DTYPES[output_dtype]
+        if not (mx_in or mx_out):
+            y = torch.ops.trec_amd.mx_linear_fwd(
+                x2, codes, scales, bias, K, relu, _MX_OUT_DTYPES[output_dtype]
+            )
+            return y.reshape(*lead, N)
+        out = torch.ops.trec_amd.mx_linear_fwd_act(
+            x2, x.scales if mx_in else None, codes, scales, bias, K, relu,
+            _MX_OUT_MXFP8 if mx_out else _MX_OUT_DTYPES[output_dtype],
         )
-        return y.reshape(*lead, codes.shape[0])
+        return MxActivation(out[0], out[1], N) if mx_out else out[0]
     from torchrec_amd.distributed import qcomm_codecs as qc
 
-    N, Kp = codes.shape
-    xq = qc.mx_decode_reference(
-        qc.mx_encode_reference(_mx_rows(x2, Kp).reshape(-1), "mxfp8"), x2.shape[0] * Kp, "mxfp8"
-    ).reshape(-1, Kp)
-    wire = torch.cat([codes.reshape(N, Kp // 32, 32), scales.reshape(N, Kp // 32, 1)], dim=2)
-    wq = qc.mx_decode_reference(wire.reshape(-1).view(torch.int8), N * Kp, "mxfp8").reshape(N, Kp)
-    y = xq @ wq.t()
+    if mx_in:
+        xq = _mx_dequant(x.codes, x.scales)
+    else:
+        xq = qc.mx_decode_reference(
+            qc.mx_encode_reference(_mx_rows(x2, Kp).reshape(-1), "mxfp8"), x2.shape[0] * Kp, "mxfp8"
+        ).reshape(-1, Kp)
+    y = xq @ _mx_dequant(codes, scales).t()
     if bias is not None:
         y = y + bias.float()
     if relu:
         y = torch.relu(y)
+    if mx_out:
+        Np = -(-N // MX_LINEAR_K_STEP) * MX_LINEAR_K_STEP
+        wire = qc.mx_encode_reference(_mx_rows(y, Np).reshape(-1), "mxfp8")
+        return MxActivation(*_mx_split(wire, y.shape[0], Np), N)
     return y.to(output_dtype).reshape(*lead, N)

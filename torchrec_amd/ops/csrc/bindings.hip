@@ -197,6 +197,11 @@ std::tuple<at::Tensor, at::Tensor> mx_linear_pack_weight(const at::Tensor& W);
 at::Tensor mx_linear_fwd(const at::Tensor& x, const at::Tensor& codes, const at::Tensor& scales,
                          const c10::optional<at::Tensor>& bias, int64_t K, bool relu,
                          int64_t output_dtype);
+std::vector<at::Tensor> mx_linear_fwd_act(const at::Tensor& x,
+                                          const c10::optional<at::Tensor>& x_scales,
+                                          const at::Tensor& codes, const at::Tensor& scales,
+                                          const c10::optional<at::Tensor>& bias, int64_t K,
+                                          bool relu, int64_t output_format);
 int64_t mx_linear_widest_tile();
 
 }  // namespace trec_amd
@@ -347,6 +352,9 @@ TORCH_LIBRARY(trec_amd, m) {
   m.def(
       "mx_linear_fwd(Tensor x, Tensor codes, Tensor scales, Tensor? bias, int K, bool relu,"
       " int output_dtype=0) -> Tensor");
+  m.def(
+      "mx_linear_fwd_act(Tensor x, Tensor? x_scales, Tensor codes, Tensor scales, Tensor? bias,"
+      " int K, bool relu, int output_format) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
@@ -406,6 +414,7 @@ TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
   m.impl("qcomm_mx_decode", trec_amd::qcomm_mx_decode);
   m.impl("mx_linear_pack_weight", trec_amd::mx_linear_pack_weight);
   m.impl("mx_linear_fwd", trec_amd::mx_linear_fwd);
+  m.impl("mx_linear_fwd_act", trec_amd::mx_linear_fwd_act);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {

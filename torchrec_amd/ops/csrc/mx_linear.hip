@@ -54,12 +54,37 @@
 // Rows, columns and k outside the matrices read as zero, never as memory;
 // stores are clipped. One launch on the current stream, no host sync, no
 // allocation but the output.
+//
+// MXFP8 between layers (XT / OT = uint8_t). An activation may arrive, and a
+// result may leave, as the pair a packed weight is: codes uint8 [M, Kp] and
+// scales uint8 [M, Kp / 32], groups of 32 consecutive features of a row.
+//   in   the [BM, 128] code slice takes the weight codes' road (16-B chunks,
+//        the same swizzle) and one scale dword per row and step lands in
+//        kAScale: no float load, no amax, no convert. The K walk and the MFMA
+//        sequence of an output element are those of the float-in path.
+//   out  after bias and ReLU the epilogue quantizes groups of 32 output
+//        columns. A lane holds columns 4 (l >> 4) + i of row l & 15 of a
+//        16 x 16 tile, so a group is two adjacent tiles and its amax spans
+//        the four l >> 4 lane groups of both: the lane's values in registers,
+//        then lane ^ 16 and lane ^ 32. Big tile: a wave's 64 columns are
+//        contiguous, both tiles are its own. Small tile: its two waves hold
+//        one half each and swap their 16 row maxima through the stage buffers,
+//        which are free after the K walk's last barrier, at one more barrier
+//        (measured against a one-wave 16 x 32 instantiation, which was 18-29%
+//        slower per layer: half the lanes issue the stage's loads). Columns
+//        at or past N count as zero. Each lane stores one dword of four codes
+//        per tile and one lane per row and group the scale byte. The last
+//        column workgroup also writes the padding up to Np = N rounded up to
+//        128 (zero codes, scale 0), so the pair is the next layer's operand
+//        as it stands.
 
 #include <torch/extension.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
 #include <tuple>
+#include <type_traits>
+#include <vector>
 
 #include "common.h"
 #include "mx_quant.h"
@@ -185,16 +210,35 @@ __device__ __forceinline__ li32x8 operand(const char* tile, int row, int kb) {
                 static_cast<int>(hi[2]), static_cast<int>(hi[3])};
 }
 
+// max over the four l >> 4 lane groups of a wave (all 64 lanes take part)
+__device__ __forceinline__ unsigned kb4_umax(unsigned a, int l) {
+  a = mumax(a, static_cast<unsigned>(
+                   __builtin_amdgcn_ds_bpermute((l ^ 16) << 2, static_cast<int>(a))));
+  a = mumax(a, static_cast<unsigned>(
+                   __builtin_amdgcn_ds_bpermute((l ^ 32) << 2, static_cast<int>(a))));
+  return a;
+}
+
+// XT uint8_t: x is the activation's codes [M, Kp] and xscales its scale bytes
+// [M, Kp / 32]. OT uint8_t: y is the result's codes [M, Np] and yscales its
+// scale bytes [M, Np / 32], Np = N rounded up to 128.
 template <typename XT, typename OT, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(WM* WN * 64) void mx_linear_fwd_kernel(
-    const XT* __restrict__ x, const uint8_t* __restrict__ wcodes,
-    const uint8_t* __restrict__ wscales, const float* __restrict__ bias /* or nullptr */,
-    int64_t M, int N, int K, int Kp, bool x_vec, bool relu, OT* __restrict__ y) {
+    const XT* __restrict__ x, const uint8_t* __restrict__ xscales,
+    const uint8_t* __restrict__ wcodes, const uint8_t* __restrict__ wscales,
+    const float* __restrict__ bias /* or nullptr */, int64_t M, int N, int K, int Kp, bool x_vec,
+    bool relu, OT* __restrict__ y, uint8_t* __restrict__ yscales) {
+  constexpr bool kMxIn = std::is_same_v<XT, uint8_t>, kMxOut = std::is_same_v<OT, uint8_t>;
   constexpr int T = WM * WN * 64;
   constexpr int TM = BM / 16 / WM, TN = BN / 16 / WN;  // MFMA tiles per wave
   constexpr int NW = BN * 8 / T;                       // 16-B weight chunks per thread
-  constexpr int NA = BM * 32 / T;                      // 4-k activation slots per thread
+  // activation per thread: 16-B code chunks, or 4-k float slots
+  constexpr int NA = kMxIn ? BM * 8 / T : BM * 32 / T;
   static_assert(BM % (16 * WM) == 0 && BN % (16 * WN) == 0 && NW >= 1 && NA >= 1 && BN <= T);
+  // MXFP8 out: a wave holds both 16 x 16 tiles of each of its 32-column groups,
+  // or (the 16 x 32 tile) one tile of the group its two waves share
+  constexpr int HT = TN == 1 ? 1 : 2, NG = TN == 1 ? 1 : TN / 2;
+  static_assert(BM <= T && (!kMxOut || TN % 2 == 0 || (TN == 1 && TM == 1 && WM == 1 && WN == 2)));
   using S = Stage<BM, BN>;
   __shared__ __attribute__((aligned(16))) char lds[2 * S::kBytes];
 
@@ -206,8 +250,8 @@ __global__ __launch_bounds__(WM* WN * 64) void mx_linear_fwd_kernel(
   const int steps = Kp / kKStep;
 
   lu32x4 rw[NW];
-  unsigned rws = 0;
-  lf32x4 ra[NA];
+  unsigned rws = 0, ras = 0;
+  std::conditional_t<kMxIn, lu32x4, lf32x4> ra[NA];
 
   auto fetch = [&](int s) {
     const int k0 = s * kKStep;
@@ -223,12 +267,28 @@ __global__ __launch_bounds__(WM* WN * 64) void mx_linear_fwd_kernel(
       rws = n0 + t < N ? *reinterpret_cast<const unsigned*>(
                              wscales + static_cast<int64_t>(n0 + t) * G + (k0 >> 5))
                        : 0u;
+    if constexpr (kMxIn) {
 #pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int c = t + i * T;
-      const int row = c >> 5;
-      ra[i] = m0 + row < M ? load4_clipped(x + (m0 + row) * K, k0 + (c % kSlotsPerRow) * 4, K, x_vec)
-                           : lf32x4{0.f, 0.f, 0.f, 0.f};
+      for (int i = 0; i < NA; ++i) {
+        const int c = t + i * T;
+        const int row = c >> 3;
+        ra[i] = m0 + row < M ? *reinterpret_cast<const lu32x4*>(x + (m0 + row) * Kp + k0 +
+                                                                (c & 7) * 16)
+                             : lu32x4{0u, 0u, 0u, 0u};
+      }
+      if (t < BM)
+        ras = m0 + t < M
+                  ? *reinterpret_cast<const unsigned*>(xscales + (m0 + t) * G + (k0 >> 5))
+                  : 0u;
+    } else {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const int c = t + i * T;
+        const int row = c >> 5;
+        ra[i] = m0 + row < M
+                    ? load4_clipped(x + (m0 + row) * K, k0 + (c % kSlotsPerRow) * 4, K, x_vec)
+                    : lf32x4{0.f, 0.f, 0.f, 0.f};
+      }
     }
   };
   auto commit = [&](int s) {
@@ -241,14 +301,25 @@ __global__ __launch_bounds__(WM* WN * 64) void mx_linear_fwd_kernel(
           rw[i];
     }
     if (t < BN) *reinterpret_cast<unsigned*>(buf + S::kWScale + t * 4) = rws;
+    if constexpr (kMxIn) {
 #pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int c = t + i * T;
-      const int row = c >> 5, q = c % kSlotsPerRow;
-      unsigned codes, sb;
-      quant4(ra[i], codes, sb);
-      *reinterpret_cast<unsigned*>(buf + S::kACodes + row * kKStep + lswz(row, q * 4)) = codes;
-      if ((q & 7) == 0) buf[S::kAScale + row * 4 + (q >> 3)] = static_cast<char>(sb);
+      for (int i = 0; i < NA; ++i) {
+        const int c = t + i * T;
+        const int row = c >> 3;
+        *reinterpret_cast<lu32x4*>(buf + S::kACodes + row * kKStep + lswz(row, (c & 7) * 16)) =
+            ra[i];
+      }
+      if (t < BM) *reinterpret_cast<unsigned*>(buf + S::kAScale + t * 4) = ras;
+    } else {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const int c = t + i * T;
+        const int row = c >> 5, q = c % kSlotsPerRow;
+        unsigned codes, sb;
+        quant4(ra[i], codes, sb);
+        *reinterpret_cast<unsigned*>(buf + S::kACodes + row * kKStep + lswz(row, q * 4)) = codes;
+        if ((q & 7) == 0) buf[S::kAScale + row * 4 + (q >> 3)] = static_cast<char>(sb);
+      }
     }
   };
 
@@ -298,36 +369,104 @@ __global__ __launch_bounds__(WM* WN * 64) void mx_linear_fwd_kernel(
     lsync();
   }
 
-  const bool n_vec = (N & 3) == 0;
+  if constexpr (kMxOut) {
+    // Every column of the tile is stored (n0 + BN <= Np); only rows clip.
+    const int Np = (N + kKStep - 1) / kKStep * kKStep, Gn = Np >> 5;
 #pragma unroll
-  for (int mi = 0; mi < TM; ++mi)
+    for (int mi = 0; mi < TM; ++mi) {
+      if (mi < tmv) {  // wave-uniform: the lane exchange below sees all 64 lanes
+        const int64_t row = m0 + (wm * TM + mi) * 16 + (l & 15);
 #pragma unroll
-    for (int ni = 0; ni < TN; ++ni) {
-      const int64_t row = m0 + (wm * TM + mi) * 16 + (l & 15);
-      const int col = n0 + (wn * TN + ni) * 16 + (kb << 2);
-      if (mi < tmv && ni < tnv && row < M && col < N) {
-        lf32x4 o = acc[mi][ni];
+        for (int gi = 0; gi < NG; ++gi) {
+          const int col = n0 + (wn * TN + HT * gi) * 16 + (kb << 2);
+          lf32x4 o[HT];
+          unsigned b[HT][4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (bias != nullptr && col + i < N) o[i] += bias[col + i];
-          if (relu) o[i] = o[i] < 0.f ? 0.f : o[i];
-        }
-        OT* dst = y + row * N + col;
-        if (n_vec) {
-          if constexpr (sizeof(OT) == 4) {
-            *reinterpret_cast<lf32x4*>(dst) = o;
-          } else {
-            *reinterpret_cast<lbf16x4*>(dst) =
-                lbf16x4{static_cast<__bf16>(o[0]), static_cast<__bf16>(o[1]),
-                        static_cast<__bf16>(o[2]), static_cast<__bf16>(o[3])};
+          for (int h = 0; h < HT; ++h) {
+            o[h] = acc[mi][HT * gi + h];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const int c = col + h * 16 + i;
+              if (bias != nullptr && c < N) o[h][i] += bias[c];
+              if (relu) o[h][i] = o[h][i] < 0.f ? 0.f : o[h][i];
+              if (c >= N) o[h][i] = 0.f;
+              b[h][i] = mbits(o[h][i]);
+            }
           }
-        } else {
+          using F = MxFmt<kFmtMxfp8>;
+          unsigned amax = mx_amax4(b[0][0], b[0][1], b[0][2], b[0][3]);
+          if constexpr (HT == 2) amax = mumax(amax, mx_amax4(b[1][0], b[1][1], b[1][2], b[1][3]));
+          amax = kb4_umax(amax, l);
+          if constexpr (HT == 1) {
+            // the other half of the group is the neighbouring wave's: swap
+            // row maxima through the stage, free since the K walk's last
+            // barrier (one row tile, so every wave arrives exactly once)
+            unsigned* xch = reinterpret_cast<unsigned*>(lds);
+            if (kb == 0) xch[w * 16 + (l & 15)] = amax;
+            lsync();
+            amax = mumax(amax, xch[(w ^ 1) * 16 + (l & 15)]);
+          }
+          const MxScale sc = mx_scale_of<F::kEmax, F::kMantMax>(amax);
+          const float inv = mpow2(-sc.E);
+          if (row < M) {
+            uint8_t* dst = y + row * Np + col;
 #pragma unroll
-          for (int i = 0; i < 4; ++i)
-            if (col + i < N) dst[i] = static_cast<OT>(o[i]);
+            for (int h = 0; h < HT; ++h) {
+              const unsigned c = mx_fp8_pack4(o[h][0], o[h][1], o[h][2], o[h][3], inv, b[h][0],
+                                              b[h][1], b[h][2], b[h][3]);
+              *reinterpret_cast<unsigned*>(dst + h * 16) = sc.special ? 0u : c;
+            }
+            if (kb == 0 && (HT == 2 || wn == 0))
+              yscales[row * Gn + (col >> 5)] = static_cast<uint8_t>(sc.byte);
+          }
         }
       }
     }
+    // the padding groups between the last column tile and Np
+    const int pad0 = n0 + BN;
+    if (pad0 >= N && pad0 < Np) {
+      const int pg = (Np - pad0) >> 5;  // 1 to 3 groups, eight code dwords each
+      for (int idx = t; idx < BM * pg * 8; idx += T) {
+        const int r = idx / (pg * 8), d = idx - r * (pg * 8);
+        if (m0 + r < M) *reinterpret_cast<unsigned*>(y + (m0 + r) * Np + pad0 + d * 4) = 0u;
+      }
+      for (int idx = t; idx < BM * pg; idx += T) {
+        const int r = idx / pg, g = idx - r * pg;
+        if (m0 + r < M) yscales[(m0 + r) * Gn + (pad0 >> 5) + g] = 0;
+      }
+    }
+  } else {
+    const bool n_vec = (N & 3) == 0;
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < TN; ++ni) {
+        const int64_t row = m0 + (wm * TM + mi) * 16 + (l & 15);
+        const int col = n0 + (wn * TN + ni) * 16 + (kb << 2);
+        if (mi < tmv && ni < tnv && row < M && col < N) {
+          lf32x4 o = acc[mi][ni];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if (bias != nullptr && col + i < N) o[i] += bias[col + i];
+            if (relu) o[i] = o[i] < 0.f ? 0.f : o[i];
+          }
+          OT* dst = y + row * N + col;
+          if (n_vec) {
+            if constexpr (sizeof(OT) == 4) {
+              *reinterpret_cast<lf32x4*>(dst) = o;
+            } else {
+              *reinterpret_cast<lbf16x4*>(dst) =
+                  lbf16x4{static_cast<__bf16>(o[0]), static_cast<__bf16>(o[1]),
+                          static_cast<__bf16>(o[2]), static_cast<__bf16>(o[3])};
+            }
+          } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              if (col + i < N) dst[i] = static_cast<OT>(o[i]);
+          }
+        }
+      }
+  }
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -345,20 +484,137 @@ bool mx_pick_big(int64_t M, int64_t N) {
   return ((M + kBigBM - 1) / kBigBM) * ((N + kBigBN - 1) / kBigBN) >= kNumCU;
 }
 
+// What the launch needs beyond the element types. xscales / yscales are null
+// unless that side is MXFP8.
+struct FwdArgs {
+  const void* x;
+  const uint8_t* xscales;
+  const uint8_t *codes, *scales;
+  const float* bias;
+  int64_t M;
+  int N, K, Kp;
+  bool x_vec, relu;
+  void* y;
+  uint8_t* yscales;
+};
+
 template <typename XT, typename OT>
-void launch_fwd(const void* x, const uint8_t* codes, const uint8_t* scales, const float* bias,
-                int64_t M, int N, int K, int Kp, bool x_vec, bool relu, void* y) {
-  const XT* xp = static_cast<const XT*>(x);
-  OT* yp = static_cast<OT*>(y);
-  if (mx_pick_big(M, N)) {
-    const dim3 grid((M + kBigBM - 1) / kBigBM, (N + kBigBN - 1) / kBigBN);
+void launch_fwd(const FwdArgs& a) {
+  const XT* xp = static_cast<const XT*>(a.x);
+  OT* yp = static_cast<OT*>(a.y);
+  if (mx_pick_big(a.M, a.N)) {
+    const dim3 grid((a.M + kBigBM - 1) / kBigBM, (a.N + kBigBN - 1) / kBigBN);
     hipLaunchKernelGGL((mx_linear_fwd_kernel<XT, OT, kBigBM, kBigBN, 2, 2>), grid, dim3(256), 0,
-                       mxl_stream(), xp, codes, scales, bias, M, N, K, Kp, x_vec, relu, yp);
+                       mxl_stream(), xp, a.xscales, a.codes, a.scales, a.bias, a.M, a.N, a.K, a.Kp,
+                       a.x_vec, a.relu, yp, a.yscales);
   } else {
-    const dim3 grid((M + kSmallBM - 1) / kSmallBM, (N + kSmallBN - 1) / kSmallBN);
+    const dim3 grid((a.M + kSmallBM - 1) / kSmallBM, (a.N + kSmallBN - 1) / kSmallBN);
     hipLaunchKernelGGL((mx_linear_fwd_kernel<XT, OT, kSmallBM, kSmallBN, 1, 2>), grid, dim3(128),
-                       0, mxl_stream(), xp, codes, scales, bias, M, N, K, Kp, x_vec, relu, yp);
+                       0, mxl_stream(), xp, a.xscales, a.codes, a.scales, a.bias, a.M, a.N, a.K,
+                       a.Kp, a.x_vec, a.relu, yp, a.yscales);
   }
+}
+
+template <typename XT>
+void launch_fwd_out(const FwdArgs& a, int64_t output_format) {
+  if (output_format == 0)
+    launch_fwd<XT, float>(a);
+  else if (output_format == 1)
+    launch_fwd<XT, __bf16>(a);
+  else
+    launch_fwd<XT, uint8_t>(a);
+}
+
+// x: fp32 / bf16 [M, K], or with xscales the codes [M, Kp] of an MXFP8
+// activation. output_format: 0 fp32, 1 bf16, 2 MXFP8 (y is then the codes
+// [M, Np] and the second tensor the scales [M, Np / 32]; otherwise the second
+// tensor is undefined).
+std::tuple<at::Tensor, at::Tensor> mx_fwd(const char* op, const at::Tensor& x,
+                                          const c10::optional<at::Tensor>& xscales,
+                                          const at::Tensor& codes, const at::Tensor& scales,
+                                          const c10::optional<at::Tensor>& bias, int64_t K,
+                                          bool relu, int64_t output_format) {
+  const bool mx_in = xscales.has_value() && xscales->defined();
+  TORCH_CHECK(K >= 1 && K < (int64_t{1} << 30), op, ": K is ", K);
+  const int64_t Kp = (K + kKStep - 1) / kKStep * kKStep;
+  if (mx_in) {
+    TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.scalar_type() == at::kByte &&
+                    x.size(1) == Kp && x.is_contiguous(),
+                op, ": activation codes must be contiguous uint8 [M, ", Kp, "] on the GPU");
+    TORCH_CHECK(xscales->is_cuda() && xscales->scalar_type() == at::kByte &&
+                    xscales->dim() == 2 && xscales->size(0) == x.size(0) &&
+                    xscales->size(1) == Kp / 32 && xscales->is_contiguous() &&
+                    xscales->device() == x.device(),
+                op, ": activation scales must be contiguous uint8 [M, ", Kp / 32,
+                "] on the codes' device");
+    TORCH_CHECK(x.size(0) == 0 || (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+                                   reinterpret_cast<uintptr_t>(xscales->data_ptr()) % 4 == 0),
+                op, ": activation codes must be 16-byte and scales 4-byte aligned");
+  } else {
+    TORCH_CHECK(x.is_cuda() && x.dim() == 2 &&
+                    (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16),
+                op, ": x must be an fp32 or bf16 [M, K] GPU tensor");
+    TORCH_CHECK(x.size(1) == K, op, ": x has ", x.size(1), " columns, K is ", K);
+  }
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 2 &&
+                  codes.size(1) == Kp && codes.is_contiguous() && codes.size(0) >= 1,
+              op, ": codes must be contiguous uint8 [N, ", Kp, "]");
+  const int64_t N = codes.size(0);
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == at::kByte && scales.dim() == 2 &&
+                  scales.size(0) == N && scales.size(1) == Kp / 32 && scales.is_contiguous(),
+              op, ": scales must be contiguous uint8 [N, ", Kp / 32, "]");
+  TORCH_CHECK(codes.device() == x.device() && scales.device() == x.device(), op, ": codes (",
+              codes.device(), ") and scales (", scales.device(), ") must be on x's device (",
+              x.device(), ")");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(scales.data_ptr()) % 4 == 0,
+              op, ": codes must be 16-byte and scales 4-byte aligned");
+  TORCH_CHECK(N < (int64_t{1} << 31) - kBigBN && N / kSmallBN < 65535, op, ": N too large");
+  TORCH_CHECK(output_format >= 0 && output_format <= 2, op,
+              ": output format must be 0 (fp32), 1 (bf16) or 2 (mxfp8), got ", output_format);
+  const float* bp = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat && bias->numel() == N &&
+                    bias->is_contiguous() && bias->device() == x.device(),
+                op, ": bias must be a contiguous fp32 [N] tensor on x's device");
+    bp = bias->data_ptr<float>();
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  const int64_t M = x.size(0);
+  at::Tensor y, ys;
+  if (output_format == 2) {
+    const int64_t Np = (N + kKStep - 1) / kKStep * kKStep;
+    y = at::empty({M, Np}, x.options().dtype(at::kByte));
+    ys = at::empty({M, Np / 32}, x.options().dtype(at::kByte));
+  } else {
+    y = at::empty({M, N}, x.options().dtype(output_format == 1 ? at::kBFloat16 : at::kFloat));
+  }
+  if (M == 0) return {y, ys};
+  const at::Tensor xc = x.contiguous();
+  const bool is_f32 = xc.scalar_type() == at::kFloat;
+  FwdArgs a;
+  a.x = xc.data_ptr();
+  a.xscales = mx_in ? xscales->data_ptr<uint8_t>() : nullptr;
+  a.codes = codes.data_ptr<uint8_t>();
+  a.scales = scales.data_ptr<uint8_t>();
+  a.bias = bp;
+  a.M = M;
+  a.N = static_cast<int>(N);
+  a.K = static_cast<int>(K);
+  a.Kp = static_cast<int>(Kp);
+  a.x_vec = !mx_in && K % 4 == 0 &&
+            reinterpret_cast<uintptr_t>(xc.data_ptr()) % (is_f32 ? 16 : 8) == 0;
+  a.relu = relu;
+  a.y = y.data_ptr();
+  a.yscales = output_format == 2 ? ys.data_ptr<uint8_t>() : nullptr;
+  if (mx_in)
+    launch_fwd_out<uint8_t>(a, output_format);
+  else if (is_f32)
+    launch_fwd_out<float>(a, output_format);
+  else
+    launch_fwd_out<__bf16>(a, output_format);
+  TREC_HIP_CHECK(hipGetLastError());
+  return {y, ys};
 }
 
 }  // namespace
@@ -389,56 +645,24 @@ std::tuple<at::Tensor, at::Tensor> mx_linear_pack_weight(const at::Tensor& W) {
 at::Tensor mx_linear_fwd(const at::Tensor& x, const at::Tensor& codes, const at::Tensor& scales,
                          const c10::optional<at::Tensor>& bias, int64_t K, bool relu,
                          int64_t output_dtype) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 &&
-                  (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16),
-              "mx_linear_fwd: x must be an fp32 or bf16 [M, K] GPU tensor");
-  TORCH_CHECK(K >= 1 && x.size(1) == K, "mx_linear_fwd: x has ", x.size(1), " columns, K is ", K);
-  const int64_t Kp = (K + kKStep - 1) / kKStep * kKStep;
-  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 2 &&
-                  codes.size(1) == Kp && codes.is_contiguous() && codes.size(0) >= 1,
-              "mx_linear_fwd: codes must be contiguous uint8 [N, ", Kp, "]");
-  const int64_t N = codes.size(0);
-  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == at::kByte && scales.dim() == 2 &&
-                  scales.size(0) == N && scales.size(1) == Kp / 32 && scales.is_contiguous(),
-              "mx_linear_fwd: scales must be contiguous uint8 [N, ", Kp / 32, "]");
-  TORCH_CHECK(codes.device() == x.device() && scales.device() == x.device(),
-              "mx_linear_fwd: codes (", codes.device(), ") and scales (", scales.device(),
-              ") must be on x's device (", x.device(), ")");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(scales.data_ptr()) % 4 == 0,
-              "mx_linear_fwd: codes must be 16-byte and scales 4-byte aligned");
-  TORCH_CHECK(N < (int64_t{1} << 31) - kBigBN && N / kSmallBN < 65535,
-              "mx_linear_fwd: N too large");
   TORCH_CHECK(output_dtype == 0 || output_dtype == 1,
               "mx_linear_fwd: output_dtype must be 0 (fp32) or 1 (bf16), got ", output_dtype);
-  const float* bp = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat && bias->numel() == N &&
-                    bias->is_contiguous() && bias->device() == x.device(),
-                "mx_linear_fwd: bias must be a contiguous fp32 [N] tensor on x's device");
-    bp = bias->data_ptr<float>();
-  }
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-  const int64_t M = x.size(0);
-  at::Tensor y = at::empty({M, N}, x.options().dtype(output_dtype == 1 ? at::kBFloat16 : at::kFloat));
-  if (M == 0) return y;
-  const at::Tensor xc = x.contiguous();
-  const bool is_f32 = xc.scalar_type() == at::kFloat;
-  const bool x_vec =
-      K % 4 == 0 && reinterpret_cast<uintptr_t>(xc.data_ptr()) % (is_f32 ? 16 : 8) == 0;
-  const uint8_t* cp = codes.data_ptr<uint8_t>();
-  const uint8_t* sp = scales.data_ptr<uint8_t>();
-  const int n = static_cast<int>(N), k = static_cast<int>(K), kp = static_cast<int>(Kp);
-  if (is_f32 && output_dtype == 0)
-    launch_fwd<float, float>(xc.data_ptr(), cp, sp, bp, M, n, k, kp, x_vec, relu, y.data_ptr());
-  else if (is_f32)
-    launch_fwd<float, __bf16>(xc.data_ptr(), cp, sp, bp, M, n, k, kp, x_vec, relu, y.data_ptr());
-  else if (output_dtype == 0)
-    launch_fwd<__bf16, float>(xc.data_ptr(), cp, sp, bp, M, n, k, kp, x_vec, relu, y.data_ptr());
-  else
-    launch_fwd<__bf16, __bf16>(xc.data_ptr(), cp, sp, bp, M, n, k, kp, x_vec, relu, y.data_ptr());
-  TREC_HIP_CHECK(hipGetLastError());
-  return y;
+  return std::get<0>(
+      mx_fwd("mx_linear_fwd", x, c10::nullopt, codes, scales, bias, K, relu, output_dtype));
+}
+
+// The forms with an MXFP8 activation on either side: x_scales given, x is the
+// codes of an activation of K features; output_format 2, the result is
+// {codes [M, Np], scales [M, Np / 32]} instead of {y}.
+std::vector<at::Tensor> mx_linear_fwd_act(const at::Tensor& x,
+                                          const c10::optional<at::Tensor>& x_scales,
+                                          const at::Tensor& codes, const at::Tensor& scales,
+                                          const c10::optional<at::Tensor>& bias, int64_t K,
+                                          bool relu, int64_t output_format) {
+  auto [y, ys] =
+      mx_fwd("mx_linear_fwd_act", x, x_scales, codes, scales, bias, K, relu, output_format);
+  if (output_format == 2) return {y, ys};
+  return {y};
 }
 
 }  // namespace trec_amd
