@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from torchrec_amd.modules.embedding_modules import EmbeddingBagCollection
-from torchrec_amd.modules.mlp import MLP
+from torchrec_amd.modules.mlp import MLP, LogitLinear
 from torchrec_amd.sparse.jagged_tensor import KeyedJaggedTensor, KeyedTensor
 
 
@@ -213,7 +213,7 @@ class OverArch(nn.Module):
         assert len(layer_sizes) >= 2, "OverArch needs at least two layers"
         self.model: nn.Module = nn.Sequential(
             MLP(in_features, layer_sizes[:-1], bias=True, activation="relu", device=device),
-            nn.Linear(layer_sizes[-2], layer_sizes[-1], bias=True, device=device),
+            LogitLinear(layer_sizes[-2], layer_sizes[-1], bias=True, device=device),
         )
 
     def forward(self, features: torch.Tensor) -> torch.Tensor:

@@ -84,6 +84,85 @@ def _use_lt_fwd() -> bool:
     )
 
 
+def _use_thin() -> bool:
+    """Vector kernels for the logit head, which is not GEMM-shaped (default
+    on; TREC_THIN_LAYERS=0 restores the GEMM path exactly). Read at call time."""
+    return os.environ.get("TREC_THIN_LAYERS", "1") == "1"
+
+
+_OUT1_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+_OUT1_PASSES = 4  # linear_out1_fwd: K <= 4 * 32 lanes * one 16 B vector
+
+
+def _aligned16(*ts: torch.Tensor) -> bool:
+    return all(t.data_ptr() % 16 == 0 for t in ts)
+
+
+def _out1_shape_ok(K: int, dt: torch.dtype) -> bool:
+    if dt not in _OUT1_DTYPES:
+        return False
+    vec = 4 if dt == torch.float32 else 8  # elements in one 16 B vector
+    return K % 8 == 0 and 0 < K <= _OUT1_PASSES * 32 * vec
+
+
+def _out1_layout_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
+    return x.is_contiguous() and w.is_contiguous() and _aligned16(x, w)
+
+
+class _LinearOut1(torch.autograd.Function):
+    """y = x @ w^T + b for one output feature: a GEMV forward kernel, and a
+    backward that reads x once for dx = dy * w and the [G, K + 1] partials of
+    dw = dy^T x and db = sum(dy), followed by one fold."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):  # type: ignore[override]
+        from torchrec_amd import ops
+
+        ops.hip_ops()
+        ctx.save_for_backward(x, w)
+        return torch.ops.trec_amd.linear_out1_fwd(x, w, b)
+
+    @staticmethod
+    def backward(ctx, dy):  # type: ignore[override]
+        x, w = ctx.saved_tensors
+        need_dx = ctx.needs_input_grad[0]
+        dx, partial = torch.ops.trec_amd.linear_out1_bwd(dy.contiguous(), x, w, need_dx)
+        dw, db = torch.ops.trec_amd.linear_out1_fold(partial, w)
+        return (dx if need_dx else None), dw, db
+
+
+class LogitLinear(nn.Linear):
+    """nn.Linear (same parameters and state_dict keys) whose one-output-feature
+    case runs as vector kernels instead of a degenerate-tile GEMM. Anything the
+    kernels do not cover takes nn.Linear.forward unchanged."""
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        if (
+            self.out_features == 1
+            and self.bias is not None
+            and not isinstance(input, torch.fx.Proxy)  # fx-trace: eager path
+            and input.is_cuda
+            and input.dim() == 2
+            and torch.is_grad_enabled()
+            and _use_thin()
+        ):
+            w, b = self.weight, self.bias
+            if torch.is_autocast_enabled("cuda"):
+                dt = torch.get_autocast_dtype("cuda")
+                if _out1_shape_ok(self.in_features, dt):
+                    with torch.autocast("cuda", enabled=False):
+                        x, w, b = input.to(dt), w.to(dt), b.to(dt)
+                        if _out1_layout_ok(x, w):
+                            return _LinearOut1.apply(x, w, b)
+            elif (
+                input.dtype == w.dtype == b.dtype
+                and _out1_shape_ok(self.in_features, w.dtype)
+                and _out1_layout_ok(input, w)
+            ):
+                return _LinearOut1.apply(input, w, b)
+        return super().forward(input)
+
+
 class _LinearReLUFused(torch.autograd.Function):
     """y = relu(x @ W^T + b); backward fuses the relu mask with the bias
     column-sum (one dY read) and split-Ks the weight gradient."""

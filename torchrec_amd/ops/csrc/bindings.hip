@@ -166,6 +166,11 @@ std::tuple<at::Tensor, at::Tensor> relu_bwd_colsum_partial(const at::Tensor& gra
                                                            const at::Tensor& y);
 std::tuple<at::Tensor, at::Tensor> splitk_fold_bias(const at::Tensor& parts,
                                                     const at::Tensor& partial);
+at::Tensor linear_out1_fwd(const at::Tensor& x, const at::Tensor& w, const at::Tensor& b);
+std::tuple<at::Tensor, at::Tensor> linear_out1_bwd(const at::Tensor& dy, const at::Tensor& x,
+                                                   const at::Tensor& w, bool need_dx);
+std::tuple<at::Tensor, at::Tensor> linear_out1_fold(const at::Tensor& partial,
+                                                    const at::Tensor& w);
 // interaction_mfma.hip
 at::Tensor interaction_mfma_forward(const at::Tensor& dense, const at::Tensor& sparse,
                                     const at::Tensor& pi, const at::Tensor& pj);
@@ -328,6 +333,9 @@ TORCH_LIBRARY(trec_amd, m) {
   m.def("relu_bwd_col_sum(Tensor grad_out, Tensor y) -> (Tensor, Tensor)");
   m.def("relu_bwd_colsum_partial(Tensor grad_out, Tensor y) -> (Tensor g, Tensor partial)");
   m.def("splitk_fold_bias(Tensor parts, Tensor partial) -> (Tensor dW, Tensor db)");
+  m.def("linear_out1_fwd(Tensor x, Tensor w, Tensor b) -> Tensor");
+  m.def("linear_out1_bwd(Tensor dy, Tensor x, Tensor w, bool need_dx) -> (Tensor dx, Tensor partial)");
+  m.def("linear_out1_fold(Tensor partial, Tensor w) -> (Tensor dw, Tensor db)");
   m.def("lt_linear_relu_fwd(Tensor x, Tensor w, Tensor b) -> Tensor");
   m.def("lt_wgrad_bgrad(Tensor g, Tensor x) -> (Tensor, Tensor)");
   m.def("relu_bwd_mask(Tensor grad_out, Tensor y) -> Tensor");
@@ -400,6 +408,9 @@ TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
   m.impl("relu_bwd_col_sum", trec_amd::relu_bwd_col_sum);
   m.impl("relu_bwd_colsum_partial", trec_amd::relu_bwd_colsum_partial);
   m.impl("splitk_fold_bias", trec_amd::splitk_fold_bias);
+  m.impl("linear_out1_fwd", trec_amd::linear_out1_fwd);
+  m.impl("linear_out1_bwd", trec_amd::linear_out1_bwd);
+  m.impl("linear_out1_fold", trec_amd::linear_out1_fold);
   m.impl("lt_linear_relu_fwd", trec_amd::lt_linear_relu_fwd);
   m.impl("lt_wgrad_bgrad", trec_amd::lt_wgrad_bgrad);
   m.impl("relu_bwd_mask", trec_amd::relu_bwd_mask);

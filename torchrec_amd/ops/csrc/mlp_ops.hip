@@ -123,10 +123,10 @@ __global__ void __launch_bounds__(kBlockThreads) relu_bwd_colsum_partial_kernel(
 constexpr int kFoldCols = 16;
 constexpr int kFoldRows = kBlockThreads / kFoldCols;  // 16
 
-template <typename o_t>
-__device__ __forceinline__ void fold_partial_tile(
+// returns the column's sum on row lane 0 (0 on the other lanes)
+__device__ __forceinline__ float fold_partial_tile_sum(
     const float* __restrict__ partial, int G, int64_t N, int64_t tile,
-    o_t* __restrict__ db, float (*red)[kFoldCols]) {
+    float (*red)[kFoldCols]) {
   const int cl = threadIdx.x % kFoldCols;
   const int rl = threadIdx.x / kFoldCols;
   const int64_t c = tile * kFoldCols + cl;
@@ -138,12 +138,21 @@ __device__ __forceinline__ void fold_partial_tile(
   }
   red[rl][cl] = acc;
   __syncthreads();
-  if (rl == 0 && c < N) {
-    float s = 0.f;
+  float s = 0.f;
+  if (rl == 0) {
 #pragma unroll
     for (int k = 0; k < kFoldRows; ++k) s += red[k][cl];
-    db[c] = float2emb(s, o_t{});
   }
+  return s;
+}
+
+template <typename o_t>
+__device__ __forceinline__ void fold_partial_tile(
+    const float* __restrict__ partial, int G, int64_t N, int64_t tile,
+    o_t* __restrict__ db, float (*red)[kFoldCols]) {
+  const float s = fold_partial_tile_sum(partial, G, N, tile, red);
+  const int64_t c = tile * kFoldCols + threadIdx.x % kFoldCols;
+  if (threadIdx.x / kFoldCols == 0 && c < N) db[c] = float2emb(s, o_t{});
 }
 
 template <typename o_t>
@@ -518,6 +527,312 @@ at::Tensor bce_with_logits_bwd(const at::Tensor& logits, const at::Tensor& label
     }
   });
   return dx;
+}
+
+// ---------------------------------------------------------------------------
+// Thin layer: Linear(K, 1), the logit head, is not GEMM-shaped: a GEMV
+// forward and an outer product + GEMV + sum backward. It is plain vector
+// code: fp32 accumulation in a fixed order, one rounding on store, no
+// atomics, no counters. The backward's partial table goes through the same
+// 16 x 16 cooperative fold as the bias gradients above.
+// ---------------------------------------------------------------------------
+
+template <typename scalar_t, int VPT>
+__device__ __forceinline__ void load_vec_f32(const scalar_t* __restrict__ p,
+                                             float (&f)[VPT]) {
+  static_assert(sizeof(scalar_t) * VPT == 16, "one 16 B vector");
+  const uint4 q = *reinterpret_cast<const uint4*>(p);
+  const scalar_t* e = reinterpret_cast<const scalar_t*>(&q);
+#pragma unroll
+  for (int v = 0; v < VPT; ++v) f[v] = emb2float(e[v]);
+}
+
+template <typename scalar_t, int VPT>
+__device__ __forceinline__ void store_vec_f32(scalar_t* __restrict__ p,
+                                              const float (&f)[VPT]) {
+  static_assert(sizeof(scalar_t) * VPT == 16, "one 16 B vector");
+  uint4 q;
+  scalar_t* e = reinterpret_cast<scalar_t*>(&q);
+#pragma unroll
+  for (int v = 0; v < VPT; ++v) e[v] = float2emb(f[v], scalar_t{});
+  *reinterpret_cast<uint4*>(p) = q;
+}
+
+// --- Linear(K, 1) forward: a half-wave per row. Lane hl owns the 16 B
+// vectors hl, hl + 32, ... of the row (NPASS of them) and keeps the matching
+// slices of w in registers; kOut1Rows rows of loads are in flight per
+// half-wave. The 32 lane sums fold by xor shuffle (16, 8, 4, 2, 1).
+constexpr int kHalfWave = 32;
+constexpr int kOut1HalfWaves = kBlockThreads / kHalfWave;  // 8
+constexpr int kOut1Rows = 4;
+constexpr int kOut1MaxPass = 4;  // K <= 4 * 32 * VPT
+
+template <typename scalar_t, int VPT, int NPASS>
+__global__ void __launch_bounds__(kBlockThreads) linear_out1_fwd_kernel(
+    const scalar_t* __restrict__ x, const scalar_t* __restrict__ w,
+    const scalar_t* __restrict__ b, int64_t M, int K, scalar_t* __restrict__ y) {
+  const int hl = threadIdx.x % kHalfWave;
+  const int hw = threadIdx.x / kHalfWave;
+  float wv[NPASS][VPT];
+#pragma unroll
+  for (int p = 0; p < NPASS; ++p) {
+    const int c = (p * kHalfWave + hl) * VPT;
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) wv[p][v] = 0.f;
+    if (c < K) load_vec_f32<scalar_t, VPT>(w + c, wv[p]);
+  }
+  const float bias = emb2float(b[0]);
+  constexpr int64_t kRowsPerBlock = kOut1HalfWaves * kOut1Rows;
+  for (int64_t rb = static_cast<int64_t>(blockIdx.x) * kRowsPerBlock; rb < M;
+       rb += static_cast<int64_t>(gridDim.x) * kRowsPerBlock) {
+    uint4 q[kOut1Rows][NPASS];
+#pragma unroll
+    for (int u = 0; u < kOut1Rows; ++u) {
+      const int64_t r = rb + u * kOut1HalfWaves + hw;
+#pragma unroll
+      for (int p = 0; p < NPASS; ++p) {
+        const int c = (p * kHalfWave + hl) * VPT;
+        q[u][p] = make_uint4(0, 0, 0, 0);
+        if (r < M && c < K) q[u][p] = *reinterpret_cast<const uint4*>(x + r * K + c);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kOut1Rows; ++u) {
+      const int64_t r = rb + u * kOut1HalfWaves + hw;
+      float acc = 0.f;
+#pragma unroll
+      for (int p = 0; p < NPASS; ++p) {
+        const scalar_t* e = reinterpret_cast<const scalar_t*>(&q[u][p]);
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) acc = fmaf(emb2float(e[v]), wv[p][v], acc);
+      }
+      // rb < M is block-uniform, so every lane of the wave reaches the shuffle
+      acc = group_reduce_sum<kHalfWave>(acc);
+      if (hl == 0 && r < M) y[r] = float2emb(acc + bias, scalar_t{});
+    }
+  }
+}
+
+// --- Linear(K, 1) backward, one pass over x: thread (rl, cl) owns one 16 B
+// column vector and the rows rl, rl + 8, ... of a contiguous row group. It
+// writes dx[m, :] = dy[m] * w and accumulates dy[m] * x[m, :] and dy[m]; the
+// 8 row lanes fold through LDS in ascending order into one partial row per
+// block, the dy sum in column K.
+constexpr int kOut1ColLanes = 32;
+constexpr int kOut1RowLanes = kBlockThreads / kOut1ColLanes;  // 8
+
+template <typename scalar_t, int VPT, bool NEED_DX>
+__global__ void __launch_bounds__(kBlockThreads) linear_out1_bwd_kernel(
+    const scalar_t* __restrict__ dy, const scalar_t* __restrict__ x,
+    const scalar_t* __restrict__ w, int64_t M, int K, int64_t rows_per_group,
+    scalar_t* __restrict__ dx, float* __restrict__ partial /* [gridDim.y, K + 1] */) {
+  constexpr int TILE_K = kOut1ColLanes * VPT;
+  __shared__ float red[kOut1RowLanes][TILE_K];
+  __shared__ float red_dy[kOut1RowLanes];
+  const int cl = threadIdx.x % kOut1ColLanes;
+  const int rl = threadIdx.x / kOut1ColLanes;
+  const int c0 = static_cast<int>(blockIdx.x) * TILE_K + cl * VPT;
+  const int64_t r0 = static_cast<int64_t>(blockIdx.y) * rows_per_group;
+  const int64_t r1 = min(M, r0 + rows_per_group);
+  float acc[VPT], wv[VPT];
+  float acc_dy = 0.f;
+#pragma unroll
+  for (int v = 0; v < VPT; ++v) acc[v] = wv[v] = 0.f;
+  if (c0 < K) {
+    if constexpr (NEED_DX) load_vec_f32<scalar_t, VPT>(w + c0, wv);
+    for (int64_t r = r0 + rl; r < r1; r += kOut1RowLanes * kRowUnroll) {
+      uint4 q[kRowUnroll];
+      float d[kRowUnroll];
+#pragma unroll
+      for (int u = 0; u < kRowUnroll; ++u) {
+        const int64_t rr = r + u * kOut1RowLanes;
+        q[u] = make_uint4(0, 0, 0, 0);
+        d[u] = 0.f;
+        if (rr < r1) {
+          q[u] = *reinterpret_cast<const uint4*>(x + rr * K + c0);
+          d[u] = emb2float(dy[rr]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kRowUnroll; ++u) {
+        const int64_t rr = r + u * kOut1RowLanes;
+        if (rr < r1) {
+          const scalar_t* e = reinterpret_cast<const scalar_t*>(&q[u]);
+          acc_dy += d[u];
+#pragma unroll
+          for (int v = 0; v < VPT; ++v) acc[v] = fmaf(d[u], emb2float(e[v]), acc[v]);
+          if constexpr (NEED_DX) {
+            float o[VPT];
+#pragma unroll
+            for (int v = 0; v < VPT; ++v) o[v] = d[u] * wv[v];
+            store_vec_f32<scalar_t, VPT>(dx + rr * K + c0, o);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < VPT; ++v) red[rl][cl * VPT + v] = acc[v];
+  if (cl == 0) red_dy[rl] = acc_dy;
+  __syncthreads();
+  float* prow = partial + static_cast<int64_t>(blockIdx.y) * (K + 1);
+  if (threadIdx.x < TILE_K) {
+    const int c = static_cast<int>(blockIdx.x) * TILE_K + threadIdx.x;
+    if (c < K) {
+      float s = 0.f;
+#pragma unroll
+      for (int k = 0; k < kOut1RowLanes; ++k) s += red[k][threadIdx.x];
+      prow[c] = s;
+    }
+  }
+  // column tile 0 always holds column 0, so its cl == 0 lanes saw every row
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < kOut1RowLanes; ++k) s += red_dy[k];
+    prow[K] = s;
+  }
+}
+
+// Fold partial [G, K + 1] into dw [1, K] and db [1]: the bias-gradient fold
+// over K + 1 columns, with a store that sends column K to db.
+template <typename o_t>
+__global__ void __launch_bounds__(kBlockThreads) linear_out1_fold_kernel(
+    const float* __restrict__ partial, int G, int K, o_t* __restrict__ dw,
+    o_t* __restrict__ db) {
+  __shared__ float red[kFoldRows][kFoldCols];
+  const float s = fold_partial_tile_sum(partial, G, K + 1, blockIdx.x, red);
+  const int c = static_cast<int>(blockIdx.x) * kFoldCols + threadIdx.x % kFoldCols;
+  if (threadIdx.x / kFoldCols == 0 && c <= K) {
+    if (c < K) dw[c] = float2emb(s, o_t{});
+    else db[0] = float2emb(s, o_t{});
+  }
+}
+
+// whole row tiles per group, then drop the groups the rounding left empty
+static inline void row_groups(int64_t M, int row_lanes, int64_t max_groups, int64_t* G,
+                              int64_t* rows_per_group) {
+  const int64_t row_tiles = (M + row_lanes - 1) / row_lanes;
+  const int64_t g = std::max<int64_t>(1, std::min(max_groups, row_tiles));
+  *rows_per_group = (row_tiles + g - 1) / g * row_lanes;
+  *G = (M + *rows_per_group - 1) / *rows_per_group;
+}
+
+#define TREC_THIN_DISPATCH(TYPE, NAME, ...)                                         \
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::kHalf, at::kBFloat16, TYPE, NAME, [&] {       \
+    if constexpr (std::is_same_v<scalar_t, double>) {                               \
+      TORCH_CHECK(false, "fp64 unsupported");                                       \
+    } else {                                                                        \
+      using dev_t = typename DevType<scalar_t>::type;                               \
+      constexpr int VPT = 16 / sizeof(dev_t);                                       \
+      __VA_ARGS__();                                                                \
+    }                                                                               \
+  })
+
+template <typename dev_t>
+static inline dev_t* dev_ptr(const at::Tensor& t) {
+  return reinterpret_cast<dev_t*>(t.data_ptr());
+}
+
+static void check_out1_args(const at::Tensor& x, const at::Tensor& w) {
+  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 2 && w.dim() == 2);
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous());
+  TORCH_CHECK(w.size(0) == 1 && w.size(1) == x.size(1) && x.scalar_type() == w.scalar_type());
+  const int64_t K = x.size(1);
+  const int64_t vpt = 16 / x.element_size();
+  TORCH_CHECK(K > 0 && K % 8 == 0 && K <= kOut1MaxPass * kHalfWave * vpt,
+              "linear_out1: K must be a multiple of 8 and at most ",
+              kOut1MaxPass * kHalfWave * vpt);
+  TORCH_CHECK(aligned16(x.data_ptr()) && aligned16(w.data_ptr()),
+              "linear_out1: operands must be 16 B-aligned");
+}
+
+// y [M, 1] = x [M, K] @ w [1, K]^T + b [1]
+at::Tensor linear_out1_fwd(const at::Tensor& x, const at::Tensor& w, const at::Tensor& b) {
+  check_out1_args(x, w);
+  TORCH_CHECK(b.is_cuda() && b.numel() == 1 && b.scalar_type() == x.scalar_type());
+  const int64_t M = x.size(0);
+  const int K = static_cast<int>(x.size(1));
+  auto y = at::empty({M, 1}, x.options());
+  if (M == 0) return y;
+  auto stream = mlp_stream();
+  TREC_THIN_DISPATCH(x.scalar_type(), "linear_out1_fwd", [&] {
+    const int grid = grid_for(M, kOut1HalfWaves * kOut1Rows);
+    const int passes = (K + kHalfWave * VPT - 1) / (kHalfWave * VPT);
+    auto launch = [&](auto np) {
+      hipLaunchKernelGGL((linear_out1_fwd_kernel<dev_t, VPT, decltype(np)::value>),
+                         dim3(grid), dim3(kBlockThreads), 0, stream, dev_ptr<const dev_t>(x),
+                         dev_ptr<const dev_t>(w), dev_ptr<const dev_t>(b), M, K,
+                         dev_ptr<dev_t>(y));
+    };
+    if (passes == 1) launch(std::integral_constant<int, 1>{});
+    else if (passes == 2) launch(std::integral_constant<int, 2>{});
+    else launch(std::integral_constant<int, kOut1MaxPass>{});
+  });
+  return y;
+}
+
+// dy [M, 1], x [M, K], w [1, K] -> dx [M, K] = dy * w (empty unless need_dx)
+// and partial [G, K + 1] fp32: columns 0..K-1 the dy * x partial sums of a
+// row group, column K its dy sum.
+std::tuple<at::Tensor, at::Tensor> linear_out1_bwd(const at::Tensor& dy, const at::Tensor& x,
+                                                   const at::Tensor& w, bool need_dx) {
+  check_out1_args(x, w);
+  const int64_t M = x.size(0);
+  const int K = static_cast<int>(x.size(1));
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.numel() == M &&
+              dy.scalar_type() == x.scalar_type());
+  auto dx = need_dx ? at::empty_like(x) : at::empty({0}, x.options());
+  int64_t G = 0, rows_per_group = 0;
+  if (M > 0)
+    row_groups(M, kOut1RowLanes, std::min<int64_t>(kMaxGroups, kPartialElems / (K + 1)), &G,
+               &rows_per_group);
+  auto partial = at::empty({G, K + 1}, x.options().dtype(at::kFloat));
+  if (M == 0) return {dx, partial};
+  auto stream = mlp_stream();
+  TREC_THIN_DISPATCH(x.scalar_type(), "linear_out1_bwd", [&] {
+    dim3 grid(static_cast<unsigned>((K + kOut1ColLanes * VPT - 1) / (kOut1ColLanes * VPT)),
+              static_cast<unsigned>(G));
+    if (need_dx) {
+      hipLaunchKernelGGL((linear_out1_bwd_kernel<dev_t, VPT, true>), grid,
+                         dim3(kBlockThreads), 0, stream, dev_ptr<const dev_t>(dy),
+                         dev_ptr<const dev_t>(x), dev_ptr<const dev_t>(w), M, K,
+                         rows_per_group, dev_ptr<dev_t>(dx), partial.data_ptr<float>());
+    } else {
+      hipLaunchKernelGGL((linear_out1_bwd_kernel<dev_t, VPT, false>), grid,
+                         dim3(kBlockThreads), 0, stream, dev_ptr<const dev_t>(dy),
+                         dev_ptr<const dev_t>(x), dev_ptr<const dev_t>(w), M, K,
+                         rows_per_group, static_cast<dev_t*>(nullptr),
+                         partial.data_ptr<float>());
+    }
+  });
+  return {dx, partial};
+}
+
+// partial [G, K + 1] fp32 (linear_out1_bwd) -> dw [1, K], db [1] in w's dtype
+std::tuple<at::Tensor, at::Tensor> linear_out1_fold(const at::Tensor& partial,
+                                                    const at::Tensor& w) {
+  TORCH_CHECK(partial.is_cuda() && partial.dim() == 2 && partial.is_contiguous() &&
+              partial.scalar_type() == at::kFloat && partial.size(1) >= 2);
+  const int64_t G = partial.size(0);
+  const int K = static_cast<int>(partial.size(1) - 1);
+  auto dw = at::empty({1, K}, w.options());
+  auto db = at::empty({1}, w.options());
+  if (G == 0) {  // an empty batch: the sums are empty
+    dw.zero_();
+    db.zero_();
+    return {dw, db};
+  }
+  TORCH_CHECK(G <= INT32_MAX);
+  const int tiles = (K + 1 + kFoldCols - 1) / kFoldCols;
+  auto stream = mlp_stream();
+  TREC_THIN_DISPATCH(w.scalar_type(), "linear_out1_fold", [&] {
+    (void)VPT;
+    hipLaunchKernelGGL((linear_out1_fold_kernel<dev_t>), dim3(tiles), dim3(kBlockThreads), 0,
+                       stream, partial.data_ptr<float>(), static_cast<int>(G), K,
+                       dev_ptr<dev_t>(dw), dev_ptr<dev_t>(db));
+  });
+  return {dw, db};
 }
 
 }  // namespace trec_amd
