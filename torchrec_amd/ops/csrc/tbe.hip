@@ -8,7 +8,8 @@
 // Design (not a port):
 //  * all tables of a group live in ONE flat fp32 weights buffer; per-table
 //    element offsets are 16B-aligned so rows load as float4.
-//  * forward: each wave serves SLOTS = 64/LPS bags concurrently; a bag's
+//  * forward: each wave runs 64/LPS slots; a slot takes tiles of consecutive
+//    bags and keeps a flight of rows loading across bag boundaries; a bag's
 //    pooled row is accumulated in fp32 registers (CHUNKS x float4 per lane),
 //    gathered rows stream through L2/LDS-free (gather has no reuse;
 //    guideline: rely on L2/L3 for hot rows).
@@ -104,7 +105,177 @@ static inline hipStream_t tbe_stream() {
 // forward (pooled)
 // ---------------------------------------------------------------------------
 
-template <typename emb_t, typename o_t, int LPS, int CHUNKS>
+// A slot of LPS lanes takes a TILE of up to LPS consecutive bags of one
+// feature. Its lanes fetch the tile's offsets in one coalesced load; the
+// positions of consecutive bags are one contiguous range, so indices, psw and
+// cache_loc come LPS positions per coalesced round and go round with __shfl.
+// Row loads are issued in flights that cross bag boundaries (the one-hot
+// flagship keeps 4 bags' rows in flight per slot); the accumulate that
+// follows walks the bags in position order, so every bag still sums
+// acc = fma(w, v, acc) over its positions ascending from zero, scales for
+// mean and rounds once. Only the loads moved (docs/KERNELS.md, TBE forward).
+
+// rows a slot keeps in flight between waits; loads outstanding per lane stay
+// at TREC_FWD_FLIGHT whatever CHUNKS is (as TREC_BWD_FLIGHT in the backward)
+#ifndef TREC_FWD_FLIGHT
+#define TREC_FWD_FLIGHT 4
+#endif
+template <int CHUNKS>
+constexpr int fwd_flight() {
+  return TREC_FWD_FLIGHT / CHUNKS > 0 ? TREC_FWD_FLIGHT / CHUNKS : 1;
+}
+
+// what a tile reads, resolved once per tile
+template <typename emb_t>
+struct FwdTileSrc {
+  const emb_t* tab;             // the feature's table
+  const float* cache_weights;   // lxu cache rows, cache_stride apart
+  int64_t cache_stride;
+  int D;
+  int sl;
+  bool weighted;
+};
+
+// loop-carried state of a tile: the bag being accumulated
+template <typename o_t, int LPS, int CHUNKS>
+struct FwdTileWalk {
+  float4 acc[CHUNKS];
+  // positions are relative to the tile's first one, offsets[bag0]: a batch
+  // holds fewer than 2^31 of them (checked on the host)
+  int32_t my_r;    // offsets[bag0 + min(lane, n)] - offsets[bag0]
+  int32_t r_end;   // offsets[bag0 + n] - offsets[bag0]
+  int32_t cs, ce;  // positions [cs, ce) of bag cb
+  int cb;          // bag within the tile
+  o_t* orow;       // output row of bag cb, at the feature's column
+  int64_t total_D;
+  bool mean_pool;
+
+  // offsets[bag0 + k], 1 <= k <= n: lanes n.. hold the closing offset, and
+  // lane LPS does not exist
+  __device__ __forceinline__ int32_t bag_end(int k) const {
+    const int32_t v = __shfl(my_r, k & (LPS - 1), LPS);
+    return k < LPS ? v : r_end;
+  }
+
+  // scale, round and store bag cb, then clear the accumulator
+  __device__ __forceinline__ void close_bag(int D, int sl) {
+    float scale = 1.f;
+    if (mean_pool && ce > cs) scale = 1.f / static_cast<float>(ce - cs);
+#pragma unroll
+    for (int c = 0; c < CHUNKS; ++c) {
+      int col4 = c * LPS + sl;
+      if (col4 * 4 < D) {
+        Vec4<o_t>::store(orow, col4,
+                         make_float4(acc[c].x * scale, acc[c].y * scale,
+                                     acc[c].z * scale, acc[c].w * scale));
+      }
+      acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+
+  __device__ __forceinline__ void next_bag() {
+    ++cb;
+    orow += total_D;
+    cs = ce;
+    ce = bag_end(cb + 1);
+  }
+};
+
+// N positions p..p+N-1 (entries j..j+N-1 of the current round): N row loads
+// issued back to back, then the accumulate in position order, closing every
+// bag that ends before the position. Straight-line loads: a lane outside the
+// row (col4 * 4 >= D) loads the row's last vector and skips the accumulate.
+// CACHED picks per position between the lxu row and the table row; only the
+// chosen one is loaded (the table of a cached module sits behind PCIe).
+template <typename emb_t, typename o_t, int LPS, int CHUNKS, int N, bool CACHED>
+__device__ __forceinline__ void fwd_flight_rows(
+    const FwdTileSrc<emb_t>& src, int64_t my_idx, float my_w, int32_t my_loc, int j,
+    int32_t p, FwdTileWalk<o_t, LPS, CHUNKS>& st) {
+  float4 v[N][CHUNKS];
+  float w[N];
+  const int D = src.D, sl = src.sl;
+  const int last4 = D / 4 - 1;
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const emb_t* row = src.tab + __shfl(my_idx, j + u, LPS) * D;
+    w[u] = src.weighted ? __shfl(my_w, j + u, LPS) : 1.f;
+    if constexpr (CACHED) {
+      const int32_t loc = __shfl(my_loc, j + u, LPS);
+      if (loc >= 0) {
+        const float* crow = src.cache_weights + static_cast<int64_t>(loc) * src.cache_stride;
+#pragma unroll
+        for (int c = 0; c < CHUNKS; ++c)
+          v[u][c] = Vec4<float>::load(crow, min(c * LPS + sl, last4));
+      } else {
+#pragma unroll
+        for (int c = 0; c < CHUNKS; ++c)
+          v[u][c] = Vec4<emb_t>::load(row, min(c * LPS + sl, last4));
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < CHUNKS; ++c)
+        v[u][c] = Vec4<emb_t>::load(row, min(c * LPS + sl, last4));
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    // p + u < p_end = the end of the tile's last bag, so cb stays inside it
+    while (p + u >= st.ce) {
+      st.close_bag(D, sl);
+      st.next_bag();
+    }
+#pragma unroll
+    for (int c = 0; c < CHUNKS; ++c) {
+      int col4 = c * LPS + sl;
+      if (col4 * 4 < D) {
+        // an explicit fma: left to contraction, the flights of 2 and 1 came
+        // out as a multiply and an add
+        st.acc[c].x = __builtin_fmaf(w[u], v[u][c].x, st.acc[c].x);
+        st.acc[c].y = __builtin_fmaf(w[u], v[u][c].y, st.acc[c].y);
+        st.acc[c].z = __builtin_fmaf(w[u], v[u][c].z, st.acc[c].z);
+        st.acc[c].w = __builtin_fmaf(w[u], v[u][c].w, st.acc[c].w);
+      }
+    }
+  }
+}
+
+// one round: cnt <= LPS positions from pb, 1 <= cnt. A lane past the round
+// re-reads the round's last position, which the slot reads anyway.
+template <typename emb_t, typename o_t, int LPS, int CHUNKS, bool CACHED>
+__device__ __forceinline__ void fwd_round(
+    const FwdTileSrc<emb_t>& src, const int64_t* __restrict__ indices,
+    const float* __restrict__ psw, const int32_t* __restrict__ cache_loc, int64_t p0,
+    int32_t pb, int cnt, FwdTileWalk<o_t, LPS, CHUNKS>& st) {
+  constexpr int U = fwd_flight<CHUNKS>();
+  static_assert(U <= 8 && LPS % U == 0, "a flight never straddles a round");
+  const int64_t pi = p0 + pb + min(src.sl, cnt - 1);
+  const int64_t my_idx = indices[pi];
+  const float my_w = src.weighted ? psw[pi] : 1.f;
+  int32_t my_loc = -1;
+  if constexpr (CACHED) my_loc = cache_loc[pi];
+  int j = 0;
+  for (; j + U <= cnt; j += U)
+    fwd_flight_rows<emb_t, o_t, LPS, CHUNKS, U, CACHED>(src, my_idx, my_w, my_loc, j, pb + j,
+                                                        st);
+  if (U > 4 && cnt - j >= 4) {
+    fwd_flight_rows<emb_t, o_t, LPS, CHUNKS, 4, CACHED>(src, my_idx, my_w, my_loc, j, pb + j,
+                                                        st);
+    j += 4;
+  }
+  if (U > 2 && cnt - j >= 2) {
+    fwd_flight_rows<emb_t, o_t, LPS, CHUNKS, 2, CACHED>(src, my_idx, my_w, my_loc, j, pb + j,
+                                                        st);
+    j += 2;
+  }
+  if (U > 1 && cnt - j >= 1)
+    fwd_flight_rows<emb_t, o_t, LPS, CHUNKS, 1, CACHED>(src, my_idx, my_w, my_loc, j, pb + j,
+                                                        st);
+}
+
+// CACHED is a kernel parameter and no branch: sharing one kernel, the cached
+// arm's registers cost the plain one its occupancy (75 against 61 VGPRs on
+// the flagship instance)
+template <typename emb_t, typename o_t, int LPS, int CHUNKS, bool CACHED>
 __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_pooled_kernel(
     const emb_t* __restrict__ weights,
     const int64_t* __restrict__ table_elem_offsets,  // [T]
@@ -114,58 +285,56 @@ __global__ void __launch_bounds__(kBlockThreads) tbe_fwd_pooled_kernel(
     const int64_t* __restrict__ indices,
     const int64_t* __restrict__ offsets,  // [F*B+1] feature-major bags
     const float* __restrict__ psw,        // nullable per-sample weights
-    const float* __restrict__ cache_weights,   // nullable lxu cache rows
-    const int32_t* __restrict__ cache_loc,     // per-position slot or -1
+    const float* __restrict__ cache_weights,   // lxu cache rows (CACHED)
+    const int32_t* __restrict__ cache_loc,     // per-position slot or -1 (CACHED)
     int64_t cache_stride,
-    int F, int B, int64_t total_D, bool mean_pool,
+    int F, int B, int tile_bags /* <= LPS */, int64_t total_D, bool mean_pool,
     o_t* __restrict__ out /* [B, total_D] */) {
-  constexpr int SLOTS = kWaveSize / LPS;
-  int sl = threadIdx.x % LPS;                    // lane within slot
-  int64_t slot = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / LPS;
-  int64_t n_slots = (static_cast<int64_t>(gridDim.x) * blockDim.x) / LPS;
-  (void)SLOTS;
-  int64_t n_bags = static_cast<int64_t>(F) * B;
-  for (int64_t bag = slot; bag < n_bags; bag += n_slots) {
-    int f = bag / B;
-    int b = bag - static_cast<int64_t>(f) * B;
-    int t = feat_table[f];
-    int D = dims[t];
-    const emb_t* tab = weights + table_elem_offsets[t];
-    float4 acc[CHUNKS];
+  const int sl = threadIdx.x % LPS;  // lane within slot
+  const int64_t slot = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / LPS;
+  const int64_t n_slots = (static_cast<int64_t>(gridDim.x) * blockDim.x) / LPS;
+  // tiles do not straddle a feature: the last tile of each feature is ragged
+  const int64_t tiles_per_feat = (static_cast<int64_t>(B) + tile_bags - 1) / tile_bags;
+  const int64_t n_tiles = tiles_per_feat * F;
+  for (int64_t tile = slot; tile < n_tiles; tile += n_slots) {
+    const int f = static_cast<int>(tile / tiles_per_feat);
+    const int b0 = static_cast<int>(tile - f * tiles_per_feat) * tile_bags;
+    const int n = min(tile_bags, B - b0);  // 1 <= n <= LPS: bags of this tile
+    const int64_t bag0 = static_cast<int64_t>(f) * B + b0;
+    const int t = feat_table[f];
+    FwdTileSrc<emb_t> src;
+    src.D = dims[t];
+    src.tab = weights + table_elem_offsets[t];
+    src.cache_weights = cache_weights;
+    src.cache_stride = cache_stride;
+    src.sl = sl;
+    src.weighted = psw != nullptr;
+    FwdTileWalk<o_t, LPS, CHUNKS> st;
+    // bag0 + n <= F * B, the last entry of offsets
+    const int64_t my_o = offsets[bag0 + min(sl, n)];
+    const int64_t o_end = offsets[bag0 + n];  // same round; lane LPS does not exist
+    const int64_t p0 = __shfl(my_o, 0, LPS);
+    st.my_r = static_cast<int32_t>(my_o - p0);
+    st.r_end = static_cast<int32_t>(o_end - p0);
+    st.total_D = total_D;
+    st.mean_pool = mean_pool;
+    st.orow = out + static_cast<int64_t>(b0) * total_D + d_out_offsets[f];
 #pragma unroll
-    for (int c = 0; c < CHUNKS; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-    int64_t i0 = offsets[bag], i1 = offsets[bag + 1];
-    for (int64_t i = i0; i < i1; ++i) {
-      int64_t idx = indices[i];
-      const emb_t* row = tab + idx * D;
-      const float* crow = nullptr;
-      if (cache_loc && cache_loc[i] >= 0) {
-        crow = cache_weights + static_cast<int64_t>(cache_loc[i]) * cache_stride;
-      }
-      float w = psw ? psw[i] : 1.f;
-#pragma unroll
-      for (int c = 0; c < CHUNKS; ++c) {
-        int col4 = c * LPS + sl;
-        if (col4 * 4 < D) {
-          float4 v = crow ? Vec4<float>::load(crow, col4) : Vec4<emb_t>::load(row, col4);
-          acc[c].x += w * v.x;
-          acc[c].y += w * v.y;
-          acc[c].z += w * v.z;
-          acc[c].w += w * v.w;
-        }
-      }
+    for (int c = 0; c < CHUNKS; ++c) st.acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    st.cb = 0;
+    st.cs = 0;
+    st.ce = st.bag_end(1);
+    // an empty tile (r_end == 0) reads no index at all
+    for (int32_t pb = 0; pb < st.r_end; pb += LPS) {
+      const int cnt = min(LPS, st.r_end - pb);
+      fwd_round<emb_t, o_t, LPS, CHUNKS, CACHED>(src, indices, psw, cache_loc, p0, pb, cnt,
+                                                 st);
     }
-    float scale = 1.f;
-    if (mean_pool && i1 > i0) scale = 1.f / static_cast<float>(i1 - i0);
-    o_t* orow = out + static_cast<int64_t>(b) * total_D + d_out_offsets[f];
-#pragma unroll
-    for (int c = 0; c < CHUNKS; ++c) {
-      int col4 = c * LPS + sl;
-      if (col4 * 4 < D) {
-        Vec4<o_t>::store(orow, col4,
-                         make_float4(acc[c].x * scale, acc[c].y * scale,
-                                     acc[c].z * scale, acc[c].w * scale));
-      }
+    // the bag in hand, then the empty bags behind it
+    for (;;) {
+      st.close_bag(src.D, sl);
+      if (st.cb + 1 >= n) break;
+      st.next_bag();
     }
   }
 }
@@ -177,16 +346,18 @@ static void launch_tbe_fwd_pooled(
     const at::Tensor& indices, const at::Tensor& offsets, const float* psw_ptr,
     const float* cache_w_ptr, const int32_t* cache_loc_ptr, int64_t max_D, int F,
     int64_t B, int64_t total_D, bool mean_pool, at::Tensor& out, int lps, int chunks,
-    int grid, hipStream_t stream) {
+    int tile_bags, int grid, hipStream_t stream) {
   o_t* out_ptr = reinterpret_cast<o_t*>(out.data_ptr<host_o_t>());
 #define TBE_FWD_LAUNCH(LPS, CHUNKS)                                                       \
-  hipLaunchKernelGGL((tbe_fwd_pooled_kernel<emb_t, o_t, LPS, CHUNKS>), dim3(grid),        \
-                     dim3(kBlockThreads), 0, stream, weights,                             \
+  hipLaunchKernelGGL((cache_loc_ptr != nullptr                                            \
+                          ? tbe_fwd_pooled_kernel<emb_t, o_t, LPS, CHUNKS, true>          \
+                          : tbe_fwd_pooled_kernel<emb_t, o_t, LPS, CHUNKS, false>),       \
+                     dim3(grid), dim3(kBlockThreads), 0, stream, weights,                 \
                      table_elem_offsets.data_ptr<int64_t>(), dims.data_ptr<int32_t>(),    \
                      feat_table.data_ptr<int32_t>(), d_out_offsets.data_ptr<int64_t>(),   \
                      indices.data_ptr<int64_t>(), offsets.data_ptr<int64_t>(),            \
-                     psw_ptr, cache_w_ptr, cache_loc_ptr, max_D, F, (int)B, total_D,      \
-                     mean_pool, out_ptr)
+                     psw_ptr, cache_w_ptr, cache_loc_ptr, max_D, F, (int)B, tile_bags,    \
+                     total_D, mean_pool, out_ptr)
   if (lps == 16) {
     TORCH_CHECK(chunks == 1);
     TBE_FWD_LAUNCH(16, 1);
@@ -224,18 +395,22 @@ at::Tensor tbe_forward_pooled(
   const int32_t* cache_loc_ptr =
       cache_loc.numel() > 0 ? cache_loc.data_ptr<int32_t>() : nullptr;
   auto stream = tbe_stream();
-  int64_t n_bags = static_cast<int64_t>(F) * B;
   // pick lanes-per-slot and register chunks from max_D
   int lps = (max_D <= 64) ? 16 : (max_D <= 128 ? 32 : 64);
   int chunks = (int)((max_D + lps * 4 - 1) / (lps * 4));
-  // grid-strided (capped) launch: unlike the backward, the forward is
-  // BANDWIDTH-bound — same-box A/B showed the full one-slot-per-bag grid
-  // 4-10% SLOWER (55.1 vs 52.9 us fp32; block scheduling overhead with no
-  // latency chain to hide). TREC_FWD_GRID_CAP overrides.
+  // the kernel walks a tile in 32-bit positions relative to its first
+  TORCH_CHECK(indices.numel() < (int64_t{1} << 31), "TBE forward: 2^31 or more indices");
+  // one slot per tile of tile_bags <= lps bags of one feature, grid-strided
+  // past the cap (TREC_FWD_TILE_BAGS and TREC_FWD_GRID_CAP override; a cap of
+  // 1 makes a slot walk many tiles)
+  int tile_bags = lps;
+  if (const char* tb = std::getenv("TREC_FWD_TILE_BAGS"))
+    tile_bags = std::min(std::max(std::atoi(tb), 1), lps);
+  int64_t n_tiles = ((B + tile_bags - 1) / tile_bags) * F;
   int64_t fwd_cap = kMaxBlocks;
   if (const char* gc = std::getenv("TREC_FWD_GRID_CAP")) fwd_cap = std::atoll(gc);
   int grid = (int)std::min<int64_t>(
-      (n_bags * lps + kBlockThreads - 1) / kBlockThreads, std::max<int64_t>(fwd_cap, 1));
+      (n_tiles * lps + kBlockThreads - 1) / kBlockThreads, std::max<int64_t>(fwd_cap, 1));
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kHalf, at::kBFloat16, weights.scalar_type(),
                                   "tbe_fwd_pooled", [&] {
     using dev_t = typename DevType<scalar_t>::type;
@@ -247,17 +422,17 @@ at::Tensor tbe_forward_pooled(
         launch_tbe_fwd_pooled<dev_t, __hip_bfloat16, at::BFloat16>(
             wp, table_elem_offsets, dims, feat_table, d_out_offsets, indices, offsets,
             psw_ptr, cache_w_ptr, cache_loc_ptr, max_D, F, B, total_D, mean_pool, out,
-            lps, chunks, grid, stream);
+            lps, chunks, tile_bags, grid, stream);
       } else if (out_dtype == 2) {
         launch_tbe_fwd_pooled<dev_t, __half, at::Half>(
             wp, table_elem_offsets, dims, feat_table, d_out_offsets, indices, offsets,
             psw_ptr, cache_w_ptr, cache_loc_ptr, max_D, F, B, total_D, mean_pool, out,
-            lps, chunks, grid, stream);
+            lps, chunks, tile_bags, grid, stream);
       } else {
         launch_tbe_fwd_pooled<dev_t, float, float>(
             wp, table_elem_offsets, dims, feat_table, d_out_offsets, indices, offsets,
             psw_ptr, cache_w_ptr, cache_loc_ptr, max_D, F, B, total_D, mean_pool, out,
-            lps, chunks, grid, stream);
+            lps, chunks, tile_bags, grid, stream);
       }
     }
   });
