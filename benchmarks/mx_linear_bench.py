@@ -12,6 +12,10 @@ size M and per Perceptron layer, and for each arch as a whole chain:
          bf16 between the layers of a chain; bf16 in and out for one layer;
          ``mxfp8_act``: the MXFP8 codes and scales themselves between the
          layers of a chain, in and out for one layer)
+  mxfp4  the same with MXFP4 weights (``weight_format="mxfp4"``), fp32 in and
+         out; ``mxfp4_act``: MXFP4 weights with the MXFP8 pair between the
+         layers, what quantize_dense(weight_format="mxfp4",
+         activation_format="mxfp8") serves
 The mx chains are what quantize_dense serves: the last Perceptron of an arch
 returns fp32 and the over arch's final nn.Linear stays an fp32 linear, which
 also keeps its fp32 weight bytes.
@@ -21,8 +25,9 @@ path (a whole chain of calls, never one launch), after warm-up; the paths of
 a comparison alternate, --repeats windows each, reported as median and
 max - min spread in microseconds per call. ``--graph`` replays the window
 from a captured graph instead, which takes the host's launch cost out.
-Weight bytes are computed from the shapes: 4 N K (fp32), 2 N K (bf16), and
-N Kp + N Kp / 32 (codes and scale bytes, Kp = K rounded up to 128).
+Weight bytes are computed from the shapes: 4 N K (fp32), 2 N K (bf16),
+N Kp + N Kp / 32 (MXFP8 codes and scale bytes, Kp = K rounded up to 128) and
+N Kp / 2 + N Kp / 32 (MXFP4).
 Prints one JSON line.
 """
 
@@ -91,7 +96,7 @@ def _paths(layers, M, as_served=True):
     ws = [torch.randn(n, k, device="cuda") / k ** 0.5 for k, n, _, _ in layers]
     bs = [torch.randn(n, device="cuda") / 8 for _, n, _, _ in layers]
     wh, bh = [w.bfloat16() for w in ws], [b.bfloat16() for b in bs]
-    packed = [ops.mx_linear_pack_weight(w) for w in ws]
+    packed = {f: [ops.mx_linear_pack_weight(w, f) for w in ws] for f in ("mxfp8", "mxfp4")}
     x = torch.randn(M, layers[0][0], device="cuda")
     xh = x.bfloat16()
 
@@ -110,12 +115,13 @@ def _paths(layers, M, as_served=True):
     # on its own emits ``dtype``.
     last_q = max(i for i, layer in enumerate(layers) if layer[3]) if as_served else -1
 
-    def mx(x0, dtype):
+    def mx(x0, dtype, fmt="mxfp8"):
         def run():
             h = x0
-            for i, ((k, _, relu, quant), (c, s), w, b) in enumerate(zip(layers, packed, ws, bs)):
+            for i, ((k, _, relu, quant), (c, s), w, b) in enumerate(
+                    zip(layers, packed[fmt], ws, bs)):
                 if quant:
-                    h = ops.mx_linear(h, c, s, b, k, relu=relu,
+                    h = ops.mx_linear(h, c, s, b, k, relu=relu, weight_format=fmt,
                                       output_dtype=torch.float32 if i == last_q else dtype)
                 else:
                     h = torch.nn.functional.linear(h, w, b)
@@ -127,12 +133,13 @@ def _paths(layers, M, as_served=True):
     # layer timed on its own reads a pair (x packed like a weight) and emits one.
     xq = ops.MxActivation(*ops.mx_linear_pack_weight(x), layers[0][0])
 
-    def mx_act():
+    def mx_act(fmt="mxfp8"):
         def run():
             h = x if as_served else xq
-            for i, ((k, _, relu, quant), (c, s), w, b) in enumerate(zip(layers, packed, ws, bs)):
+            for i, ((k, _, relu, quant), (c, s), w, b) in enumerate(
+                    zip(layers, packed[fmt], ws, bs)):
                 if quant:
-                    h = ops.mx_linear(h, c, s, b, k, relu=relu,
+                    h = ops.mx_linear(h, c, s, b, k, relu=relu, weight_format=fmt,
                                       output_format=None if i == last_q else "mxfp8")
                 else:
                     h = torch.nn.functional.linear(h, w, b)
@@ -146,6 +153,8 @@ def _paths(layers, M, as_served=True):
         # served, the float neighbours hand the first layer fp32
         "mxfp8_bf16": mx(x if as_served else xh, torch.bfloat16),
         "mxfp8_act": mx_act(),
+        "mxfp4": mx(x, torch.float32, "mxfp4"),
+        "mxfp4_act": mx_act("mxfp4"),
     }
 
 
@@ -171,6 +180,7 @@ def main():
         out["weight_bytes"][f"{k}x{n}"] = {
             "fp32": 4 * n * k, "bf16": 2 * n * k,
             "mxfp8": n * kp + n * kp // 32 if quant else 4 * n * k,
+            "mxfp4": n * kp // 2 + n * kp // 32 if quant else 4 * n * k,
         }
     with torch.inference_mode():
         for M in args.batches:

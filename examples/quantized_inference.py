@@ -5,7 +5,8 @@ Run (1 GPU):  python examples/quantized_inference.py [--weight-dtype FP8]
 ``--weight-dtype`` is INT8, INT4, INT2 or FP8 (e4m3fn codes with a rowwise
 scale: the bytes of INT8, a relative instead of an absolute error).
 ``--dense-format mxfp8`` also swaps the dense and over arch MLPs for their
-MXFP8 forms (``inference.modules.quantize_dense``).
+MXFP8 forms (``inference.modules.quantize_dense``); ``--dense-format mxfp4``
+stores their weights as MXFP4 instead (half the bytes, activations MXFP8).
 CPU works too (reference dequant path).
 """
 
@@ -30,8 +31,9 @@ from torchrec_amd.sparse.jagged_tensor import KeyedJaggedTensor
 def main() -> None:
     parser = argparse.ArgumentParser()
     parser.add_argument("--weight-dtype", default="INT8", choices=["INT8", "INT4", "INT2", "FP8"])
-    parser.add_argument("--dense-format", default=None, choices=["mxfp8"],
-                        help="also serve the dense MLPs quantized (MXFP8 weights and activations)")
+    parser.add_argument("--dense-format", default=None, choices=["mxfp8", "mxfp4"],
+                        help="also serve the dense MLPs quantized (MXFP8 or MXFP4 weights, "
+                             "MXFP8 activations)")
     args = parser.parse_args()
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     keys = [f"cat_{i}" for i in range(4)]

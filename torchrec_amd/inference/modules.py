@@ -46,9 +46,10 @@ def quantize_inference_model(
     serves the named tables pruned. Both are
     ``QuantTableBatchedEmbeddingBags``'s arguments, by table name.
 
-    ``dense_format="mxfp8"`` also swaps the dense MLPs (``quantize_dense``
-    with ``output_dtype=dense_output_dtype``); the default leaves them as they
-    are. ``output_dtype`` is the embeddings' alone: the two are not coupled.
+    ``dense_format="mxfp8"`` or ``"mxfp4"`` (the weights' format) also swaps
+    the dense MLPs (``quantize_dense`` with
+    ``output_dtype=dense_output_dtype``); the default leaves them as they are.
+    ``output_dtype`` is the embeddings' alone: the two are not coupled.
     ``dense_activation_format`` is ``quantize_dense``'s ``activation_format``."""
     mapping = quantization_mapping or {
         FloatEBC: QuantEBC,
@@ -101,6 +102,9 @@ def quantize_dense(
     before. A lone ``Perceptron`` has no layer after it, so ``output_dtype``
     does not touch it.
 
+    ``weight_format="mxfp4"`` stores the weights as e2m1 codes (half the code
+    bytes; the activations stay MXFP8 either way).
+
     ``activation_format="mxfp8"`` makes the layers inside a swapped ``MLP``
     hand each other the MXFP8 codes and scales themselves where the layer's
     activation rides the kernel (``QuantMLP``), instead of ``output_dtype``
@@ -111,8 +115,9 @@ def quantize_dense(
     a subclass keeps its float shell (the ``Perceptron``s inside a subclassed
     ``MLP`` are still swapped one by one), and so does a ``model`` that is
     itself an ``MLP``."""
-    if weight_format != "mxfp8":
-        raise ValueError(f"quantize_dense: unknown weight_format {weight_format!r} (only 'mxfp8')")
+    if weight_format not in ("mxfp8", "mxfp4"):
+        raise ValueError(
+            f"quantize_dense: unknown weight_format {weight_format!r} ('mxfp8' | 'mxfp4')")
     if output_dtype not in (torch.float32, torch.bfloat16):
         raise ValueError(f"quantize_dense: output_dtype must be fp32 or bf16, got {output_dtype}")
     if activation_format not in (None, "mxfp8"):
@@ -137,11 +142,12 @@ def quantize_dense(
             if type(child) is MLP:
                 q = QuantMLP.from_float(
                     child, output_dtype=output_dtype, result_dtype=_float_dtype(path, child),
-                    activation_format=activation_format,
+                    activation_format=activation_format, weight_format=weight_format,
                 )
                 setattr(parent, name, q)
             elif type(child) is Perceptron:
-                q = QuantPerceptron.from_float(child, output_dtype=_float_dtype(path, child))
+                q = QuantPerceptron.from_float(child, output_dtype=_float_dtype(path, child),
+                                               weight_format=weight_format)
                 setattr(parent, name, q)
             else:
                 _swap(child, path + ".")

@@ -819,6 +819,14 @@ MX_LINEAR_K_STEP = 128  # codes are padded to a multiple of this many k
 MX_LINEAR_WIDEST_TILE = 128
 _MX_OUT_DTYPES = {torch.float32: 0, torch.bfloat16: 1}
 _MX_OUT_MXFP8 = 2  # the kernel's output-format code after the two dtypes
+# weight element formats (the ids of _MX_FMT_IDS) and the k a code byte holds
+_MX_WEIGHT_K_PER_BYTE = {"mxfp8": 1, "mxfp4": 2}
+
+
+def _mx_weight_format(weight_format: str) -> str:
+    if weight_format not in _MX_WEIGHT_K_PER_BYTE:
+        raise ValueError(f"mx_linear: unknown weight_format {weight_format!r} ('mxfp8' | 'mxfp4')")
+    return weight_format
 
 
 class MxActivation(NamedTuple):
@@ -846,35 +854,46 @@ def _mx_rows(t: torch.Tensor, width: int) -> torch.Tensor:
     return out
 
 
-def mx_linear_pack_weight(weight: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+def mx_linear_pack_weight(
+    weight: torch.Tensor, weight_format: str = "mxfp8"
+) -> Tuple[torch.Tensor, torch.Tensor]:
     """W [N, K] -> (codes uint8 [N, Kp], scales uint8 [N, Kp / 32]): MXFP8
     groups of 32 consecutive k of each row, Kp = K rounded up to 128, a
-    ragged last group quantized as if padded with zeros, padding groups zero."""
+    ragged last group quantized as if padded with zeros, padding groups zero.
+    ``weight_format="mxfp4"``: e2m1 codes uint8 [N, Kp / 2], element 2k in the
+    low and 2k + 1 in the high nibble of byte k; scales as for MXFP8."""
     assert weight.dim() == 2 and weight.shape[0] >= 1 and weight.shape[1] >= 1, tuple(weight.shape)
+    fmt = _mx_weight_format(weight_format)
     if weight.is_cuda:
         _mx_linear_ext()
-        return torch.ops.trec_amd.mx_linear_pack_weight(weight.detach().float())
+        return torch.ops.trec_amd.mx_linear_pack_weight(weight.detach().float(), _MX_FMT_IDS[fmt])
     from torchrec_amd.distributed import qcomm_codecs as qc
 
     N, K = weight.shape
     Kp = -(-K // MX_LINEAR_K_STEP) * MX_LINEAR_K_STEP
-    wire = qc.mx_encode_reference(_mx_rows(weight.detach(), Kp).reshape(-1), "mxfp8")
-    return _mx_split(wire, N, Kp)
+    wire = qc.mx_encode_reference(_mx_rows(weight.detach(), Kp).reshape(-1), fmt)
+    return _mx_split(wire, N, Kp, fmt)
 
 
-def _mx_split(wire: torch.Tensor, rows: int, width: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Reference wire of [rows, width] values -> (codes [rows, width], scales [rows, width / 32])."""
-    wire = wire.view(torch.uint8).reshape(rows, width // 32, 33)
-    return wire[:, :, :32].reshape(rows, width).contiguous(), wire[:, :, 32].contiguous()
+def _mx_split(
+    wire: torch.Tensor, rows: int, width: int, fmt: str = "mxfp8"
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Reference wire of [rows, width] values -> (codes, scales [rows, width / 32]);
+    codes are [rows, width] bytes for MXFP8 and [rows, width / 2] for MXFP4."""
+    gb = 32 // _MX_WEIGHT_K_PER_BYTE[fmt]  # code bytes of a group, then its scale byte
+    wire = wire.view(torch.uint8).reshape(rows, width // 32, gb + 1)
+    codes = wire[:, :, :gb].reshape(rows, width // 32 * gb)
+    return codes.contiguous(), wire[:, :, gb].contiguous()
 
 
-def _mx_dequant(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
-    """(codes [R, W], scales [R, W / 32]) -> fp32 [R, W] through the reference codec."""
-    R, W = codes.shape
-    wire = torch.cat([codes.reshape(R, W // 32, 32), scales.reshape(R, W // 32, 1)], dim=2)
+def _mx_dequant(codes: torch.Tensor, scales: torch.Tensor, fmt: str = "mxfp8") -> torch.Tensor:
+    """(codes, scales [R, W / 32]) -> fp32 [R, W] through the reference codec."""
+    R, G = scales.shape
+    wire = torch.cat([codes.reshape(R, G, -1), scales.reshape(R, G, 1)], dim=2)
     from torchrec_amd.distributed import qcomm_codecs as qc
 
-    return qc.mx_decode_reference(wire.reshape(-1).view(torch.int8), R * W, "mxfp8").reshape(R, W)
+    return qc.mx_decode_reference(wire.reshape(-1).view(torch.int8), R * G * 32, fmt).reshape(
+        R, G * 32)
 
 
 def mx_linear(
@@ -886,11 +905,15 @@ def mx_linear(
     relu: bool = False,
     output_dtype: torch.dtype = torch.float32,
     output_format: Optional[str] = None,
+    weight_format: str = "mxfp8",
 ) -> Union[torch.Tensor, MxActivation]:
     """y = act(Qx(x) Qw(W)^T + b) with both operands in MXFP8 (groups of 32
     consecutive k per row), fp32 accumulation, bias and ReLU on the fp32 sum,
     one rounding to ``output_dtype`` (fp32 or bf16). ``x`` is [..., K] fp32 or
-    bf16; ``codes`` / ``scales`` come from ``mx_linear_pack_weight``.
+    bf16; ``codes`` / ``scales`` come from ``mx_linear_pack_weight``. With
+    ``weight_format="mxfp4"`` they are that function's MXFP4 pair (W4A8: e2m1
+    weights against e4m3 activations in the one MFMA); x, the result and an
+    ``MxActivation`` on either side are the same as for MXFP8 weights.
 
     ``x`` may instead be the ``MxActivation`` an earlier call returned: its
     codes and scales are the operand as they stand and nothing is quantized.
@@ -902,8 +925,10 @@ def mx_linear(
     PyTorch (reference quantize / dequantize, fp32 matmul)."""
     assert output_dtype in _MX_OUT_DTYPES, f"mx_linear: output_dtype {output_dtype}"
     assert output_format in (None, "mxfp8"), f"mx_linear: output_format {output_format!r}"
+    fmt = _mx_weight_format(weight_format)
     K = in_features
-    N, Kp = codes.shape
+    N, Kp = codes.shape[0], -(-K // MX_LINEAR_K_STEP) * MX_LINEAR_K_STEP
+    assert codes.shape[1] * _MX_WEIGHT_K_PER_BYTE[fmt] == Kp, (tuple(codes.shape), K, fmt)
     mx_in, mx_out = isinstance(x, MxActivation), output_format == "mxfp8"
     if mx_in:
         assert x.features == K and x.codes.dim() == 2 and x.codes.shape[1] == Kp, (
@@ -918,12 +943,12 @@ def mx_linear(
         _mx_linear_ext()
         if not (mx_in or mx_out):
             y = torch.ops.trec_amd.mx_linear_fwd(
-                x2, codes, scales, bias, K, relu, _MX_OUT_DTYPES[output_dtype]
+                x2, codes, scales, bias, K, relu, _MX_OUT_DTYPES[output_dtype], _MX_FMT_IDS[fmt]
             )
             return y.reshape(*lead, N)
         out = torch.ops.trec_amd.mx_linear_fwd_act(
             x2, x.scales if mx_in else None, codes, scales, bias, K, relu,
-            _MX_OUT_MXFP8 if mx_out else _MX_OUT_DTYPES[output_dtype],
+            _MX_OUT_MXFP8 if mx_out else _MX_OUT_DTYPES[output_dtype], _MX_FMT_IDS[fmt],
         )
         return MxActivation(out[0], out[1], N) if mx_out else out[0]
     from torchrec_amd.distributed import qcomm_codecs as qc
@@ -934,7 +959,7 @@ def mx_linear(
         xq = qc.mx_decode_reference(
             qc.mx_encode_reference(_mx_rows(x2, Kp).reshape(-1), "mxfp8"), x2.shape[0] * Kp, "mxfp8"
         ).reshape(-1, Kp)
-    y = xq @ _mx_dequant(codes, scales).t()
+    y = xq @ _mx_dequant(codes, scales, fmt).t()
     if bias is not None:
         y = y + bias.float()
     if relu:

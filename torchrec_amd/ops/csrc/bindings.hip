@@ -198,15 +198,17 @@ void qcomm_mx_decode(const at::Tensor& wire, at::Tensor out, int64_t fmt,
                      const at::Tensor& col_off, int64_t B);
 int64_t qcomm_mx_tile_groups();
 // mx_linear.hip
-std::tuple<at::Tensor, at::Tensor> mx_linear_pack_weight(const at::Tensor& W);
+std::tuple<at::Tensor, at::Tensor> mx_linear_pack_weight(const at::Tensor& W,
+                                                         int64_t weight_format);
 at::Tensor mx_linear_fwd(const at::Tensor& x, const at::Tensor& codes, const at::Tensor& scales,
                          const c10::optional<at::Tensor>& bias, int64_t K, bool relu,
-                         int64_t output_dtype);
+                         int64_t output_dtype, int64_t weight_format);
 std::vector<at::Tensor> mx_linear_fwd_act(const at::Tensor& x,
                                           const c10::optional<at::Tensor>& x_scales,
                                           const at::Tensor& codes, const at::Tensor& scales,
                                           const c10::optional<at::Tensor>& bias, int64_t K,
-                                          bool relu, int64_t output_format);
+                                          bool relu, int64_t output_format,
+                                          int64_t weight_format);
 int64_t mx_linear_widest_tile();
 
 }  // namespace trec_amd
@@ -356,13 +358,14 @@ TORCH_LIBRARY(trec_amd, m) {
       " Tensor(a!) dx0_acc) -> (Tensor dxl, Tensor u, Tensor dt)");
   m.def("qcomm_mx_encode(Tensor src, int fmt, Tensor col_off, int B) -> Tensor");
   m.def("qcomm_mx_decode(Tensor wire, Tensor(a!) out, int fmt, Tensor col_off, int B) -> ()");
-  m.def("mx_linear_pack_weight(Tensor W) -> (Tensor codes, Tensor scales)");
+  // weight_format: 0 MXFP8 (codes [N, Kp]), 1 MXFP4 (codes [N, Kp / 2])
+  m.def("mx_linear_pack_weight(Tensor W, int weight_format=0) -> (Tensor codes, Tensor scales)");
   m.def(
       "mx_linear_fwd(Tensor x, Tensor codes, Tensor scales, Tensor? bias, int K, bool relu,"
-      " int output_dtype=0) -> Tensor");
+      " int output_dtype=0, int weight_format=0) -> Tensor");
   m.def(
       "mx_linear_fwd_act(Tensor x, Tensor? x_scales, Tensor codes, Tensor scales, Tensor? bias,"
-      " int K, bool relu, int output_format) -> Tensor[]");
+      " int K, bool relu, int output_format, int weight_format=0) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {

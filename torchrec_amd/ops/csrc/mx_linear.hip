@@ -77,6 +77,30 @@
 //        column workgroup also writes the padding up to Np = N rounded up to
 //        128 (zero codes, scale 0), so the pair is the next layer's operand
 //        as it stands.
+//
+// MXFP4 weights (WF = kFmtMxfp4, W4A8). The MFMA takes a format per operand:
+// cbsz 4 makes the first (weight) operand e2m1 in 4 VGPRs, blgp 0 leaves the
+// activations e4m3, so everything on the activation side and all three
+// epilogues are shared with WF = kFmtMxfp8. Packed weight: codes uint8
+// [N, Kp / 2] in natural order (element 2k in the low, 2k + 1 in the high
+// nibble of byte k, the qcomm codec's MXFP4 bytes), scales [N, Kp / 32] as
+// before. Operand layout, measured on the MI355X with one-hot probes (one
+// e2m1 1.0 in one nibble of one register of one lane; the e4m3 operand, in
+// the layout above, holds bit m of k in row m, so the output row spells k):
+// lane l, kb = l >> 4, supplies for operand row l & 15 the 32 nibbles of k
+// [32 kb, 32 kb + 32): register r holds k [32 kb + 8 r, 32 kb + 8 r + 8),
+// nibble i of it k 32 kb + 8 r + i. Registers 4-7 are not read. Block j's
+// scale still comes from byte 0 of the scale register of the lanes with
+// kb = j, for either operand; bytes 1-3 are ignored. So, unlike e4m3, a lane
+// group's registers ARE one MX group, and a lane reads bytes [16 kb, 16 kb +
+// 16) of the row's 64 in one 16-B piece. Stage: 64-B weight rows, four 16-B
+// chunks per row (NW = BN * 4 / T: one per thread in the small tile, two in
+// the big one, half the e4m3 count), the slot XORed with (row >> 2) & 3: four
+// rows span the banks' 256 B, so the 16 rows a lane group reads hit 16
+// different 16-B bank groups. Every e2m1 value is an e4m3 value: the decoded
+// weight repacked as MXFP8 through the e4m3 kernel gives the same result up
+// to the MFMA's internal summation (bit-equal at the three smallest test
+// shapes, within 2e-3 absolute at K = 300, 479 and 1024 on the test inputs).
 
 #include <torch/extension.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -118,6 +142,12 @@ __device__ __forceinline__ void lsync() {
 // XOR-swizzle of the 16-B slots inside a 128-B row
 __device__ __forceinline__ int lswz(int row, int byte_in_row) {
   return byte_in_row ^ ((row & 7) << 4);
+}
+// ... and of the four 16-B slots inside a 64-B row of e2m1 weight codes: four
+// rows fill the 256 B the banks span, so the slot turns with row >> 2 and the
+// 16 rows a lane group reads (one slot each) land on 16 different bank groups
+__device__ __forceinline__ int lswz4(int row, int byte_in_row) {
+  return byte_in_row ^ (((row >> 2) & 3) << 4);
 }
 
 __device__ __forceinline__ lf32x4 to_f4(lf32x4 v) { return v; }
@@ -164,8 +194,11 @@ __device__ __forceinline__ void quant4(lf32x4 v, unsigned& codes, unsigned& scal
   scale_byte = sc.byte;
 }
 
-// W [N, K] fp32 -> codes [N, Kp], scales [N, Kp / 32]. A thread owns four k
-// of one (row, group); padding groups come out as zero codes and scale 0.
+// W [N, K] fp32 -> codes [N, Kp] (WF MXFP4: [N, Kp / 2], element 2k in the
+// low nibble of byte k), scales [N, Kp / 32]. A thread owns four k of one
+// (row, group) and writes a dword (two bytes); padding groups come out as
+// zero codes and scale 0.
+template <int WF>
 __global__ __launch_bounds__(kPackThreads) void mx_linear_pack_kernel(
     const float* __restrict__ W, int64_t N, int K, int Kp, uint8_t* __restrict__ codes,
     uint8_t* __restrict__ scales) {
@@ -181,19 +214,30 @@ __global__ __launch_bounds__(kPackThreads) void mx_linear_pack_kernel(
   lf32x4 v{0.f, 0.f, 0.f, 0.f};
   if (live) v = load4_clipped(W + row * K, k, K, (K & 3) == 0);
   unsigned c, sb;
-  quant4(v, c, sb);  // every lane takes part in the DPP max
-  if (live) {
-    *reinterpret_cast<unsigned*>(codes + row * Kp + k) = c;
-    if (j == 0) scales[row * G + g] = static_cast<uint8_t>(sb);
+  if constexpr (WF == kFmtMxfp8) {
+    quant4(v, c, sb);  // every lane takes part in the DPP max
+    if (live) *reinterpret_cast<unsigned*>(codes + row * Kp + k) = c;
+  } else {
+    const unsigned b0 = mbits(v[0]), b1 = mbits(v[1]), b2 = mbits(v[2]), b3 = mbits(v[3]);
+    using F = MxFmt<kFmtMxfp4>;
+    const MxScale sc = mx_scale_of<F::kEmax, F::kMantMax>(group8_umax(mx_amax4(b0, b1, b2, b3)));
+    c = mx_fp4_pack4(v[0], v[1], v[2], v[3], mpow2(-sc.E), b0, b1, b2, b3);
+    sb = sc.byte;
+    if (live)
+      *reinterpret_cast<unsigned short*>(codes + row * (Kp >> 1) + (k >> 1)) =
+          static_cast<unsigned short>(sc.special ? 0u : c);
   }
+  if (live && j == 0) scales[row * G + g] = static_cast<uint8_t>(sb);
 }
 
 // One buffer of the stage: [weight codes | activation codes | weight scale
-// dwords | activation scale dwords]
-template <int BM, int BN>
+// dwords | activation scale dwords]. A weight row of a step is 128 B of e4m3
+// or 64 B of e2m1 codes.
+template <int WF, int BM, int BN>
 struct Stage {
+  static constexpr int kWRow = WF == kFmtMxfp4 ? kKStep / 2 : kKStep;
   static constexpr int kWCodes = 0;
-  static constexpr int kACodes = BN * kKStep;
+  static constexpr int kACodes = BN * kWRow;
   static constexpr int kWScale = kACodes + BM * kKStep;
   static constexpr int kAScale = kWScale + BN * 4;
   static constexpr int kBytes = kAScale + BM * 4;
@@ -210,6 +254,16 @@ __device__ __forceinline__ li32x8 operand(const char* tile, int row, int kb) {
                 static_cast<int>(hi[2]), static_cast<int>(hi[3])};
 }
 
+// The e2m1 weight operand of lane group kb for a row: the 32 nibbles of k
+// [32 kb, 32 kb + 32), bytes [16 kb, 16 kb + 16) of the 64-B row, in registers
+// 0-3, element 2k in the low nibble; registers 4-7 are not read (cbsz 4)
+__device__ __forceinline__ li32x8 operand4(const char* tile, int row, int kb) {
+  const lu32x4 v = *reinterpret_cast<const lu32x4*>(tile + row * (kKStep / 2) +
+                                                    lswz4(row, kb * 16));
+  return li32x8{static_cast<int>(v[0]), static_cast<int>(v[1]), static_cast<int>(v[2]),
+                static_cast<int>(v[3]), 0, 0, 0, 0};
+}
+
 // max over the four l >> 4 lane groups of a wave (all 64 lanes take part)
 __device__ __forceinline__ unsigned kb4_umax(unsigned a, int l) {
   a = mumax(a, static_cast<unsigned>(
@@ -219,10 +273,12 @@ __device__ __forceinline__ unsigned kb4_umax(unsigned a, int l) {
   return a;
 }
 
+// WF: the weights' element format, kFmtMxfp8 (wcodes [N, Kp]) or kFmtMxfp4
+// (wcodes [N, Kp / 2]); activations are MXFP8 in both.
 // XT uint8_t: x is the activation's codes [M, Kp] and xscales its scale bytes
 // [M, Kp / 32]. OT uint8_t: y is the result's codes [M, Np] and yscales its
 // scale bytes [M, Np / 32], Np = N rounded up to 128.
-template <typename XT, typename OT, int BM, int BN, int WM, int WN>
+template <int WF, typename XT, typename OT, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(WM* WN * 64) void mx_linear_fwd_kernel(
     const XT* __restrict__ x, const uint8_t* __restrict__ xscales,
     const uint8_t* __restrict__ wcodes, const uint8_t* __restrict__ wscales,
@@ -231,7 +287,9 @@ __global__ __launch_bounds__(WM* WN * 64) void mx_linear_fwd_kernel(
   constexpr bool kMxIn = std::is_same_v<XT, uint8_t>, kMxOut = std::is_same_v<OT, uint8_t>;
   constexpr int T = WM * WN * 64;
   constexpr int TM = BM / 16 / WM, TN = BN / 16 / WN;  // MFMA tiles per wave
-  constexpr int NW = BN * 8 / T;                       // 16-B weight chunks per thread
+  constexpr bool kW4 = WF == kFmtMxfp4;
+  constexpr int CW = kW4 ? 4 : 8, LW = kW4 ? 2 : 3;    // 16-B chunks of a weight row, log2
+  constexpr int NW = BN * CW / T;                      // 16-B weight chunks per thread
   // activation per thread: 16-B code chunks, or 4-k float slots
   constexpr int NA = kMxIn ? BM * 8 / T : BM * 32 / T;
   static_assert(BM % (16 * WM) == 0 && BN % (16 * WN) == 0 && NW >= 1 && NA >= 1 && BN <= T);
@@ -239,7 +297,7 @@ __global__ __launch_bounds__(WM* WN * 64) void mx_linear_fwd_kernel(
   // or (the 16 x 32 tile) one tile of the group its two waves share
   constexpr int HT = TN == 1 ? 1 : 2, NG = TN == 1 ? 1 : TN / 2;
   static_assert(BM <= T && (!kMxOut || TN % 2 == 0 || (TN == 1 && TM == 1 && WM == 1 && WN == 2)));
-  using S = Stage<BM, BN>;
+  using S = Stage<WF, BM, BN>;
   __shared__ __attribute__((aligned(16))) char lds[2 * S::kBytes];
 
   const int t = ltid(), l = t & 63, w = t >> 6;
@@ -248,6 +306,7 @@ __global__ __launch_bounds__(WM* WN * 64) void mx_linear_fwd_kernel(
   const int n0 = __builtin_amdgcn_workgroup_id_y() * BN;
   const int G = Kp >> 5;
   const int steps = Kp / kKStep;
+  const int64_t wld = kW4 ? Kp >> 1 : Kp;  // bytes of a weight code row
 
   lu32x4 rw[NW];
   unsigned rws = 0, ras = 0;
@@ -258,10 +317,11 @@ __global__ __launch_bounds__(WM* WN * 64) void mx_linear_fwd_kernel(
 #pragma unroll
     for (int i = 0; i < NW; ++i) {
       const int c = t + i * T;
-      const int row = c >> 3;
-      rw[i] = n0 + row < N ? *reinterpret_cast<const lu32x4*>(
-                                 wcodes + static_cast<int64_t>(n0 + row) * Kp + k0 + (c & 7) * 16)
-                           : lu32x4{0u, 0u, 0u, 0u};
+      const int row = c >> LW;
+      rw[i] = n0 + row < N
+                  ? *reinterpret_cast<const lu32x4*>(wcodes + static_cast<int64_t>(n0 + row) * wld +
+                                                     (kW4 ? k0 >> 1 : k0) + (c & (CW - 1)) * 16)
+                  : lu32x4{0u, 0u, 0u, 0u};
     }
     if (t < BN)
       rws = n0 + t < N ? *reinterpret_cast<const unsigned*>(
@@ -296,9 +356,9 @@ __global__ __launch_bounds__(WM* WN * 64) void mx_linear_fwd_kernel(
 #pragma unroll
     for (int i = 0; i < NW; ++i) {
       const int c = t + i * T;
-      const int row = c >> 3;
-      *reinterpret_cast<lu32x4*>(buf + S::kWCodes + row * kKStep + lswz(row, (c & 7) * 16)) =
-          rw[i];
+      const int row = c >> LW;
+      const int at = kW4 ? lswz4(row, (c & 3) * 16) : lswz(row, (c & 7) * 16);
+      *reinterpret_cast<lu32x4*>(buf + S::kWCodes + row * S::kWRow + at) = rw[i];
     }
     if (t < BN) *reinterpret_cast<unsigned*>(buf + S::kWScale + t * 4) = rws;
     if constexpr (kMxIn) {
@@ -348,7 +408,10 @@ __global__ __launch_bounds__(WM* WN * 64) void mx_linear_fwd_kernel(
 #pragma unroll
       for (int ni = 0; ni < TN; ++ni) {
         const int row = (wn * TN + ni) * 16 + (l & 15);
-        wf[ni] = operand(buf + S::kWCodes, row, kb);
+        if constexpr (kW4)
+          wf[ni] = operand4(buf + S::kWCodes, row, kb);
+        else
+          wf[ni] = operand(buf + S::kWCodes, row, kb);
         ws[ni] = static_cast<unsigned char>(buf[S::kWScale + row * 4 + kb]);
       }
 #pragma unroll
@@ -361,7 +424,7 @@ __global__ __launch_bounds__(WM* WN * 64) void mx_linear_fwd_kernel(
           for (int ni = 0; ni < TN; ++ni)
             if (ni < tnv)
               acc[mi][ni] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-                  wf[ni], af, acc[mi][ni], 0, 0, 0, ws[ni], 0, as);
+                  wf[ni], af, acc[mi][ni], kW4 ? 4 : 0, 0, 0, ws[ni], 0, as);
         }
       }
     }
@@ -498,45 +561,64 @@ struct FwdArgs {
   uint8_t* yscales;
 };
 
-template <typename XT, typename OT>
+template <int WF, typename XT, typename OT>
 void launch_fwd(const FwdArgs& a) {
   const XT* xp = static_cast<const XT*>(a.x);
   OT* yp = static_cast<OT*>(a.y);
   if (mx_pick_big(a.M, a.N)) {
     const dim3 grid((a.M + kBigBM - 1) / kBigBM, (a.N + kBigBN - 1) / kBigBN);
-    hipLaunchKernelGGL((mx_linear_fwd_kernel<XT, OT, kBigBM, kBigBN, 2, 2>), grid, dim3(256), 0,
+    hipLaunchKernelGGL((mx_linear_fwd_kernel<WF, XT, OT, kBigBM, kBigBN, 2, 2>), grid, dim3(256), 0,
                        mxl_stream(), xp, a.xscales, a.codes, a.scales, a.bias, a.M, a.N, a.K, a.Kp,
                        a.x_vec, a.relu, yp, a.yscales);
   } else {
     const dim3 grid((a.M + kSmallBM - 1) / kSmallBM, (a.N + kSmallBN - 1) / kSmallBN);
-    hipLaunchKernelGGL((mx_linear_fwd_kernel<XT, OT, kSmallBM, kSmallBN, 1, 2>), grid, dim3(128),
+    hipLaunchKernelGGL((mx_linear_fwd_kernel<WF, XT, OT, kSmallBM, kSmallBN, 1, 2>), grid, dim3(128),
                        0, mxl_stream(), xp, a.xscales, a.codes, a.scales, a.bias, a.M, a.N, a.K,
                        a.Kp, a.x_vec, a.relu, yp, a.yscales);
   }
 }
 
-template <typename XT>
+template <int WF, typename XT>
 void launch_fwd_out(const FwdArgs& a, int64_t output_format) {
   if (output_format == 0)
-    launch_fwd<XT, float>(a);
+    launch_fwd<WF, XT, float>(a);
   else if (output_format == 1)
-    launch_fwd<XT, __bf16>(a);
+    launch_fwd<WF, XT, __bf16>(a);
   else
-    launch_fwd<XT, uint8_t>(a);
+    launch_fwd<WF, XT, uint8_t>(a);
+}
+
+template <int WF>
+void launch_fwd_in(const FwdArgs& a, bool mx_in, bool is_f32, int64_t output_format) {
+  if (mx_in)
+    launch_fwd_out<WF, uint8_t>(a, output_format);
+  else if (is_f32)
+    launch_fwd_out<WF, float>(a, output_format);
+  else
+    launch_fwd_out<WF, __bf16>(a, output_format);
+}
+
+void check_weight_format(const char* op, int64_t weight_format) {
+  TORCH_CHECK(weight_format == kFmtMxfp8 || weight_format == kFmtMxfp4, op,
+              ": weight format must be 0 (mxfp8) or 1 (mxfp4), got ", weight_format);
 }
 
 // x: fp32 / bf16 [M, K], or with xscales the codes [M, Kp] of an MXFP8
 // activation. output_format: 0 fp32, 1 bf16, 2 MXFP8 (y is then the codes
 // [M, Np] and the second tensor the scales [M, Np / 32]; otherwise the second
-// tensor is undefined).
+// tensor is undefined). weight_format: kFmtMxfp8 (codes [N, Kp]) or kFmtMxfp4
+// (codes [N, Kp / 2]).
 std::tuple<at::Tensor, at::Tensor> mx_fwd(const char* op, const at::Tensor& x,
                                           const c10::optional<at::Tensor>& xscales,
                                           const at::Tensor& codes, const at::Tensor& scales,
                                           const c10::optional<at::Tensor>& bias, int64_t K,
-                                          bool relu, int64_t output_format) {
+                                          bool relu, int64_t output_format,
+                                          int64_t weight_format) {
   const bool mx_in = xscales.has_value() && xscales->defined();
+  check_weight_format(op, weight_format);
   TORCH_CHECK(K >= 1 && K < (int64_t{1} << 30), op, ": K is ", K);
   const int64_t Kp = (K + kKStep - 1) / kKStep * kKStep;
+  const int64_t wld = weight_format == kFmtMxfp4 ? Kp / 2 : Kp;
   if (mx_in) {
     TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.scalar_type() == at::kByte &&
                     x.size(1) == Kp && x.is_contiguous(),
@@ -557,8 +639,8 @@ std::tuple<at::Tensor, at::Tensor> mx_fwd(const char* op, const at::Tensor& x,
     TORCH_CHECK(x.size(1) == K, op, ": x has ", x.size(1), " columns, K is ", K);
   }
   TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 2 &&
-                  codes.size(1) == Kp && codes.is_contiguous() && codes.size(0) >= 1,
-              op, ": codes must be contiguous uint8 [N, ", Kp, "]");
+                  codes.size(1) == wld && codes.is_contiguous() && codes.size(0) >= 1,
+              op, ": codes must be contiguous uint8 [N, ", wld, "]");
   const int64_t N = codes.size(0);
   TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == at::kByte && scales.dim() == 2 &&
                   scales.size(0) == N && scales.size(1) == Kp / 32 && scales.is_contiguous(),
@@ -607,12 +689,10 @@ std::tuple<at::Tensor, at::Tensor> mx_fwd(const char* op, const at::Tensor& x,
   a.relu = relu;
   a.y = y.data_ptr();
   a.yscales = output_format == 2 ? ys.data_ptr<uint8_t>() : nullptr;
-  if (mx_in)
-    launch_fwd_out<uint8_t>(a, output_format);
-  else if (is_f32)
-    launch_fwd_out<float>(a, output_format);
+  if (weight_format == kFmtMxfp4)
+    launch_fwd_in<kFmtMxfp4>(a, mx_in, is_f32, output_format);
   else
-    launch_fwd_out<__bf16>(a, output_format);
+    launch_fwd_in<kFmtMxfp8>(a, mx_in, is_f32, output_format);
   TREC_HIP_CHECK(hipGetLastError());
   return {y, ys};
 }
@@ -621,7 +701,9 @@ std::tuple<at::Tensor, at::Tensor> mx_fwd(const char* op, const at::Tensor& x,
 
 int64_t mx_linear_widest_tile() { return kBigBN; }
 
-std::tuple<at::Tensor, at::Tensor> mx_linear_pack_weight(const at::Tensor& W) {
+std::tuple<at::Tensor, at::Tensor> mx_linear_pack_weight(const at::Tensor& W,
+                                                         int64_t weight_format) {
+  check_weight_format("mx_linear_pack_weight", weight_format);
   TORCH_CHECK(W.is_cuda() && W.dim() == 2 && W.scalar_type() == at::kFloat,
               "mx_linear_pack_weight: W must be an fp32 [N, K] GPU tensor");
   const int64_t N = W.size(0), K = W.size(1);
@@ -630,13 +712,19 @@ std::tuple<at::Tensor, at::Tensor> mx_linear_pack_weight(const at::Tensor& W) {
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(W.device());
   at::Tensor Wc = W.contiguous();
   if (reinterpret_cast<uintptr_t>(Wc.data_ptr()) % 16 != 0) Wc = Wc.clone();
-  at::Tensor codes = at::empty({N, Kp}, W.options().dtype(at::kByte));
+  const bool w4 = weight_format == kFmtMxfp4;
+  at::Tensor codes = at::empty({N, w4 ? Kp / 2 : Kp}, W.options().dtype(at::kByte));
   at::Tensor scales = at::empty({N, Kp / 32}, W.options().dtype(at::kByte));
   const int64_t slots = N * (Kp / 32) * 8;
-  hipLaunchKernelGGL(mx_linear_pack_kernel, dim3((slots + kPackThreads - 1) / kPackThreads),
-                     dim3(kPackThreads), 0, mxl_stream(), Wc.data_ptr<float>(), N,
-                     static_cast<int>(K), static_cast<int>(Kp), codes.data_ptr<uint8_t>(),
-                     scales.data_ptr<uint8_t>());
+  const dim3 grid((slots + kPackThreads - 1) / kPackThreads);
+  if (w4)
+    hipLaunchKernelGGL(mx_linear_pack_kernel<kFmtMxfp4>, grid, dim3(kPackThreads), 0, mxl_stream(),
+                       Wc.data_ptr<float>(), N, static_cast<int>(K), static_cast<int>(Kp),
+                       codes.data_ptr<uint8_t>(), scales.data_ptr<uint8_t>());
+  else
+    hipLaunchKernelGGL(mx_linear_pack_kernel<kFmtMxfp8>, grid, dim3(kPackThreads), 0, mxl_stream(),
+                       Wc.data_ptr<float>(), N, static_cast<int>(K), static_cast<int>(Kp),
+                       codes.data_ptr<uint8_t>(), scales.data_ptr<uint8_t>());
   TREC_HIP_CHECK(hipGetLastError());
   return {codes, scales};
 }
@@ -644,11 +732,12 @@ std::tuple<at::Tensor, at::Tensor> mx_linear_pack_weight(const at::Tensor& W) {
 // output_dtype: 0 fp32, 1 bf16 (the op-level code of the TBE ops)
 at::Tensor mx_linear_fwd(const at::Tensor& x, const at::Tensor& codes, const at::Tensor& scales,
                          const c10::optional<at::Tensor>& bias, int64_t K, bool relu,
-                         int64_t output_dtype) {
+                         int64_t output_dtype, int64_t weight_format) {
   TORCH_CHECK(output_dtype == 0 || output_dtype == 1,
               "mx_linear_fwd: output_dtype must be 0 (fp32) or 1 (bf16), got ", output_dtype);
   return std::get<0>(
-      mx_fwd("mx_linear_fwd", x, c10::nullopt, codes, scales, bias, K, relu, output_dtype));
+      mx_fwd("mx_linear_fwd", x, c10::nullopt, codes, scales, bias, K, relu, output_dtype,
+             weight_format));
 }
 
 // The forms with an MXFP8 activation on either side: x_scales given, x is the
@@ -658,9 +747,10 @@ std::vector<at::Tensor> mx_linear_fwd_act(const at::Tensor& x,
                                           const c10::optional<at::Tensor>& x_scales,
                                           const at::Tensor& codes, const at::Tensor& scales,
                                           const c10::optional<at::Tensor>& bias, int64_t K,
-                                          bool relu, int64_t output_format) {
-  auto [y, ys] =
-      mx_fwd("mx_linear_fwd_act", x, x_scales, codes, scales, bias, K, relu, output_format);
+                                          bool relu, int64_t output_format,
+                                          int64_t weight_format) {
+  auto [y, ys] = mx_fwd("mx_linear_fwd_act", x, x_scales, codes, scales, bias, K, relu,
+                        output_format, weight_format);
   if (output_format == 2) return {y, ys};
   return {y};
 }

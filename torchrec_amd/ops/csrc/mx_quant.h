@@ -1,6 +1,6 @@
 // Device helpers of the OCP MX quantizers (qcomm_codec.hip, mx_linear.hip):
-// group amax over eight lanes, amax -> E8M0 scale, four fp32 -> four e4m3
-// codes. The scale rule and its special cases are the ones written out at the
+// group amax over eight lanes, amax -> E8M0 scale, four fp32 -> four e4m3 or
+// four e2m1 codes. The scale rule and its special cases are the ones written out at the
 // top of qcomm_codec.hip; distributed/qcomm_codecs.py is the oracle.
 //
 // Everything here is built without the packed fp32 VALU forms (see
@@ -92,6 +92,26 @@ __device__ __forceinline__ unsigned mx_fp8_pack4(float v0, float v1, float v2, f
   const unsigned signs = ((b0 >> 31) << 7) | ((b1 >> 31) << 15) | ((b2 >> 31) << 23) |
                          ((b3 >> 31) << 31);
   return (static_cast<unsigned>(w) & 0x7F7F7F7Fu) | signs;
+}
+
+// Four values times inv = 2^-E -> four e2m1 codes in the low 16 bits,
+// element i in nibble i. The scaled convert runs with a unit scale: the
+// multiply already applied 2^-E, which also covers E = -127 (a subnormal
+// factor the instruction's exponent-only scale operand cannot carry). Clamp
+// and signs as in mx_fp8_pack4.
+__device__ __forceinline__ unsigned mx_fp4_pack4(float v0, float v1, float v2, float v3, float inv,
+                                                 unsigned b0, unsigned b1, unsigned b2,
+                                                 unsigned b3) {
+  unsigned w = 0;
+  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, __builtin_amdgcn_fmed3f(v0 * inv, -6.f, 6.f),
+                                               __builtin_amdgcn_fmed3f(v1 * inv, -6.f, 6.f), 1.0f,
+                                               0);
+  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, __builtin_amdgcn_fmed3f(v2 * inv, -6.f, 6.f),
+                                               __builtin_amdgcn_fmed3f(v3 * inv, -6.f, 6.f), 1.0f,
+                                               1);
+  const unsigned signs = ((b0 >> 31) << 3) | ((b1 >> 31) << 7) | ((b2 >> 31) << 11) |
+                         ((b3 >> 31) << 15);
+  return (w & 0x7777u) | signs;
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)

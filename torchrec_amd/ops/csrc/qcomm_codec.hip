@@ -164,18 +164,8 @@ __global__ __launch_bounds__(kMxThreads) void qcomm_mx_encode_kernel(
             mx_fp8_pack4(v[p][0], v[p][1], v[p][2], v[p][3], inv, b0, b1, b2, b3);
         *reinterpret_cast<mu32_u*>(gp + 4 * j) = special ? 0u : codes;
       } else {
-        // scaled convert with a unit scale: the multiply above already
-        // applied 2^-E, which also covers E = -127 (a subnormal scale)
-        unsigned w = 0;
-        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(
-            w, __builtin_amdgcn_fmed3f(v[p][0] * inv, -6.f, 6.f),
-            __builtin_amdgcn_fmed3f(v[p][1] * inv, -6.f, 6.f), 1.0f, 0);
-        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(
-            w, __builtin_amdgcn_fmed3f(v[p][2] * inv, -6.f, 6.f),
-            __builtin_amdgcn_fmed3f(v[p][3] * inv, -6.f, 6.f), 1.0f, 1);
-        const unsigned signs = ((b0 >> 31) << 3) | ((b1 >> 31) << 7) | ((b2 >> 31) << 11) |
-                               ((b3 >> 31) << 15);
-        const unsigned codes = (w & 0x7777u) | signs;
+        const unsigned codes =
+            mx_fp4_pack4(v[p][0], v[p][1], v[p][2], v[p][3], inv, b0, b1, b2, b3);
         *reinterpret_cast<mu16_u*>(gp + 2 * j) = static_cast<unsigned short>(special ? 0u : codes);
       }
       if (j == 0) gp[F::kScaleAt] = static_cast<uint8_t>(scale_byte);

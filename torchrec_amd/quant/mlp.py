@@ -8,6 +8,8 @@ GEMM kernel, products and sums are fp32, and bias and ReLU ride the kernel's
 epilogue. With ``activation_format="mxfp8"`` the layers of a ``QuantMLP`` hand
 each other the quantized activation itself (``ops.MxActivation``), so a layer
 quantizes its result once in its epilogue and the next one reads codes.
+``weight_format="mxfp4"`` stores the weight as e2m1 codes instead (two k per
+byte, the same scale bytes): half the weight bytes, activations still MXFP8.
 Inference only."""
 
 from __future__ import annotations
@@ -43,13 +45,16 @@ class QuantPerceptron(nn.Module):
         activation: Union[Callable[[torch.Tensor], torch.Tensor], nn.Module] = torch.relu,
         output_dtype: torch.dtype = torch.float32,
         activation_format: Optional[str] = None,
+        weight_format: str = "mxfp8",
     ) -> None:
         super().__init__()
+        assert weight_format in ("mxfp8", "mxfp4"), f"unknown weight_format {weight_format!r}"
         assert output_dtype in _OUTPUT_DTYPES, f"output_dtype must be fp32 or bf16, got {output_dtype}"
         assert activation_format in (None, "mxfp8"), f"unknown activation_format {activation_format!r}"
         self._in_size = in_size
         self._out_size = codes.shape[0]
         self._output_dtype = output_dtype
+        self._weight_format = weight_format
         self._activation_fn = activation
         self._relu = activation is torch.relu or isinstance(activation, nn.ReLU)
         self._identity = activation is None or isinstance(activation, nn.Identity)
@@ -64,12 +69,13 @@ class QuantPerceptron(nn.Module):
         module: Perceptron,
         output_dtype: torch.dtype = torch.float32,
         activation_format: Optional[str] = None,
+        weight_format: str = "mxfp8",
     ) -> "QuantPerceptron":
         linear = module._linear
-        codes, scales = ops.mx_linear_pack_weight(linear.weight)
+        codes, scales = ops.mx_linear_pack_weight(linear.weight, weight_format)
         bias = None if linear.bias is None else linear.bias.detach().float().clone()
         return cls(module._in_size, codes, scales, bias, module._activation_fn, output_dtype,
-                   activation_format)
+                   activation_format, weight_format)
 
     def forward(
         self, input: Union[torch.Tensor, ops.MxActivation]
@@ -80,6 +86,7 @@ class QuantPerceptron(nn.Module):
         y = ops.mx_linear(
             input, self.codes, self.scales, self.bias, self._in_size,
             relu=self._relu, output_dtype=self._output_dtype, output_format=self._output_format,
+            weight_format=self._weight_format,
         )
         return y if self._relu or self._identity else self._activation_fn(y)
 
@@ -109,6 +116,7 @@ class QuantMLP(nn.Module):
         output_dtype: torch.dtype = torch.float32,
         result_dtype: Optional[torch.dtype] = None,
         activation_format: Optional[str] = None,
+        weight_format: str = "mxfp8",
     ) -> "QuantMLP":
         last = len(module._mlp) - 1
         layers = nn.Sequential(
@@ -117,6 +125,7 @@ class QuantMLP(nn.Module):
                     p,
                     output_dtype=(result_dtype or output_dtype) if i == last else output_dtype,
                     activation_format=None if i == last else activation_format,
+                    weight_format=weight_format,
                 )
                 for i, p in enumerate(module._mlp)
             ]
