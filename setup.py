@@ -24,6 +24,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "interaction.hip"),
         os.path.join(CSRC, "interaction_mfma.hip"),
         os.path.join(CSRC, "cross_mfma.hip"),
+        os.path.join(CSRC, "mips_topk.hip"),
         os.path.join(CSRC, "qcomm_codec.hip"),
         os.path.join(CSRC, "mx_linear.hip"),
         os.path.join(CSRC, "mlp_ops.hip"),

@@ -15,6 +15,8 @@ from torchrec_amd.models.dlrm import (  # noqa: F401
 from torchrec_amd.models.two_tower import (  # noqa: F401
     SequenceTwoTower,
     TwoTower,
+    TwoTowerRetrieval,
     TwoTowerTrain,
+    build_candidate_index,
 )
 from torchrec_amd.modules.deepfm import SimpleDeepFMNN  # noqa: F401

@@ -582,6 +582,66 @@ def lowrank_cross(
     return _LowRankCross.apply(x0.contiguous(), save_t, L, *params)
 
 
+# ------------------------------------------------------------------------
+# exhaustive top-k retrieval (csrc/mips_topk.hip)
+# ------------------------------------------------------------------------
+
+MIPS_TOPK_MAX_D = 256
+MIPS_TOPK_MAX_K = 128
+
+
+def mips_topk(
+    queries: torch.Tensor,
+    corpus: torch.Tensor,
+    k: int,
+    row_bias: Optional[torch.Tensor] = None,
+    splits: int = 0,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact top-k of ``queries @ corpus.T (+ row_bias)`` per query.
+
+    queries [B, D] fp32 or bf16 (rounded to bf16, RNE); corpus [N, Dp] bf16,
+    contiguous, Dp = D rounded up to a multiple of 32 with zero pad columns;
+    row_bias fp32 [N]. Returns (scores fp32 [B, k], ids int64 [B, k]) ordered
+    by score descending, then id ascending; with N < k the tail is -inf / -1.
+    ``splits`` forces the number of corpus splits on the GPU (0: from the
+    shapes); it does not change the result. Scores must not be NaN: the GPU
+    path drops a NaN score, the CPU sort would rank it first; +-inf are ordered.
+
+    GPU: the fused score-and-select MFMA kernels, the score matrix is never
+    materialised. CPU: an fp32 matmul of the bf16 values and a stable sort.
+    """
+    if queries.dim() != 2 or corpus.dim() != 2:
+        raise ValueError("mips_topk: queries [B, D] and corpus [N, Dp] must be 2-D")
+    D, (N, Dp) = queries.shape[1], corpus.shape
+    if not 1 <= D <= MIPS_TOPK_MAX_D:
+        raise ValueError(f"mips_topk: embedding width {D} is outside 1..{MIPS_TOPK_MAX_D}")
+    if not 1 <= k <= MIPS_TOPK_MAX_K:
+        raise ValueError(f"mips_topk: k = {k} is outside 1..{MIPS_TOPK_MAX_K}")
+    if Dp % 32 != 0 or Dp != (D + 31) // 32 * 32:
+        raise ValueError(
+            f"mips_topk: corpus width {Dp} must be D = {D} rounded up to a multiple of 32"
+        )
+    if corpus.dtype != torch.bfloat16 or not corpus.is_contiguous():
+        raise ValueError("mips_topk: corpus must be a contiguous bf16 tensor")
+    if queries.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("mips_topk: queries must be fp32 or bf16")
+    if row_bias is not None and (row_bias.shape != (N,) or row_bias.dtype != torch.float32):
+        raise ValueError("mips_topk: row_bias must be an fp32 [N] tensor")
+    if queries.is_cuda:
+        hip_ops()
+        return torch.ops.trec_amd.mips_topk(queries, corpus, row_bias, k, splits)
+    scores = queries.bfloat16().float() @ corpus[:, :D].float().t()
+    if row_bias is not None:
+        scores = scores + row_bias
+    top, ids = torch.sort(scores, dim=1, descending=True, stable=True)
+    top, ids = top[:, :k], ids[:, :k]
+    if N < k:
+        pad = (queries.shape[0], k - N)
+        top = torch.cat([top, top.new_full(pad, float("-inf"))], dim=1)
+        ids = torch.cat([ids, ids.new_full(pad, -1)], dim=1)
+    return top.contiguous(), ids.contiguous()
+
+
 class _FusedBceWithLogits(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels):  # type: ignore[override]

@@ -191,6 +191,10 @@ std::tuple<at::Tensor, at::Tensor> lowrank_cross_fwd(const at::Tensor& x0, const
 std::tuple<at::Tensor, at::Tensor, at::Tensor> lowrank_cross_bwd(
     const at::Tensor& g, const at::Tensor& x0, const at::Tensor& xl, const at::Tensor& t,
     const at::Tensor& V, const at::Tensor& W, const at::Tensor& b, at::Tensor dx0_acc);
+// mips_topk.hip
+std::tuple<at::Tensor, at::Tensor> mips_topk(const at::Tensor& queries, const at::Tensor& corpus,
+                                             const c10::optional<at::Tensor>& row_bias, int64_t k,
+                                             int64_t splits);
 // qcomm_codec.hip
 at::Tensor qcomm_mx_encode(const at::Tensor& src, int64_t fmt, const at::Tensor& col_off,
                            int64_t B);
@@ -356,6 +360,10 @@ TORCH_LIBRARY(trec_amd, m) {
   m.def(
       "lowrank_cross_bwd(Tensor g, Tensor x0, Tensor xl, Tensor t, Tensor V, Tensor W, Tensor b,"
       " Tensor(a!) dx0_acc) -> (Tensor dxl, Tensor u, Tensor dt)");
+  // splits: 0 picks the corpus split count from the shapes
+  m.def(
+      "mips_topk(Tensor queries, Tensor corpus, Tensor? row_bias, int k, int splits=0)"
+      " -> (Tensor scores, Tensor ids)");
   m.def("qcomm_mx_encode(Tensor src, int fmt, Tensor col_off, int B) -> Tensor");
   m.def("qcomm_mx_decode(Tensor wire, Tensor(a!) out, int fmt, Tensor col_off, int B) -> ()");
   // weight_format: 0 MXFP8 (codes [N, Kp]), 1 MXFP4 (codes [N, Kp / 2])
@@ -424,6 +432,7 @@ TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
   m.impl("interaction_backward", trec_amd::interaction_backward);
   m.impl("lowrank_cross_fwd", trec_amd::lowrank_cross_fwd);
   m.impl("lowrank_cross_bwd", trec_amd::lowrank_cross_bwd);
+  m.impl("mips_topk", trec_amd::mips_topk);
   m.impl("qcomm_mx_encode", trec_amd::qcomm_mx_encode);
   m.impl("qcomm_mx_decode", trec_amd::qcomm_mx_decode);
   m.impl("mx_linear_pack_weight", trec_amd::mx_linear_pack_weight);
