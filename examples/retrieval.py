@@ -1,6 +1,7 @@
 """Two-tower retrieval: train a few steps, index every item, query the index.
 
-    python examples/retrieval.py [--items 5000 --users 1000 --k 10 --metric ip]
+    python examples/retrieval.py [--items 5000 --users 1000 --k 10 --metric ip
+                                  --num_centroids 64 --num_probe 8]
 """
 
 import argparse
@@ -17,7 +18,12 @@ from torchrec_amd.models import (  # noqa: E402
     TwoTowerTrain,
     build_candidate_index,
 )
-from torchrec_amd.modules import EmbeddingBagCollection, EmbeddingBagConfig, FlatIndex  # noqa: E402
+from torchrec_amd.modules import (  # noqa: E402
+    EmbeddingBagCollection,
+    EmbeddingBagConfig,
+    FlatIndex,
+    IVFFlatIndex,
+)
 from torchrec_amd.sparse.jagged_tensor import KeyedJaggedTensor  # noqa: E402
 
 
@@ -33,6 +39,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--metric", choices=["ip", "l2"], default="ip")
+    ap.add_argument("--num_centroids", type=int, default=0,
+                    help="lists of an IVF index; 0 searches exhaustively")
+    ap.add_argument("--num_probe", type=int, default=8, help="lists searched per query")
     args = ap.parse_args()
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     torch.manual_seed(0)
@@ -55,10 +64,14 @@ def main():
     print(f"trained {args.steps} steps, loss {loss.item():.3f}")
 
     all_items = torch.arange(args.items, device=device)
+    if args.num_centroids:
+        index = IVFFlatIndex(64, args.num_centroids, nprobe=args.num_probe, metric=args.metric,
+                             device=device)
+    else:
+        index = FlatIndex(64, metric=args.metric, device=device)
     index = build_candidate_index(
-        two_tower, (_one_id_per_row(["item"], [b]) for b in all_items.split(1024)),
-        FlatIndex(64, metric=args.metric, device=device))
-    print(f"indexed {len(index)} items")
+        two_tower, (_one_id_per_row(["item"], [b]) for b in all_items.split(1024)), index)
+    print(f"indexed {len(index)} items in a {type(index).__name__}")
 
     model = TwoTowerRetrieval.from_two_tower(two_tower, index, args.k)
     users = torch.arange(4, device=device)

@@ -25,6 +25,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "interaction_mfma.hip"),
         os.path.join(CSRC, "cross_mfma.hip"),
         os.path.join(CSRC, "mips_topk.hip"),
+        os.path.join(CSRC, "ivf_topk.hip"),
         os.path.join(CSRC, "qcomm_codec.hip"),
         os.path.join(CSRC, "mx_linear.hip"),
         os.path.join(CSRC, "mlp_ops.hip"),

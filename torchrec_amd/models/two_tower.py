@@ -12,7 +12,7 @@ path.
 from __future__ import annotations
 
 import dataclasses
-from typing import Dict, Iterable, List, Optional, Tuple
+from typing import Dict, Iterable, List, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -21,9 +21,11 @@ from torchrec_amd.modules.embedding_modules import (
     EmbeddingBagCollection,
     EmbeddingCollection,
 )
-from torchrec_amd.modules.knn_index import FlatIndex
+from torchrec_amd.modules.knn_index import FlatIndex, IVFFlatIndex
 from torchrec_amd.modules.mlp import MLP
 from torchrec_amd.sparse.jagged_tensor import KeyedJaggedTensor
+
+KnnIndex = Union[FlatIndex, IVFFlatIndex]
 
 
 class TwoTower(nn.Module):
@@ -104,7 +106,7 @@ class TwoTowerRetrieval(nn.Module):
 
     def __init__(
         self,
-        index: FlatIndex,
+        index: KnnIndex,
         query_ebc: EmbeddingBagCollection,
         candidate_ebc: EmbeddingBagCollection,
         query_features: List[str],
@@ -128,7 +130,7 @@ class TwoTowerRetrieval(nn.Module):
         self.candidate_proj = MLP(c_in, layer_sizes, device=device)
 
     @classmethod
-    def from_two_tower(cls, two_tower: TwoTower, index: FlatIndex, k: int) -> "TwoTowerRetrieval":
+    def from_two_tower(cls, two_tower: TwoTower, index: KnnIndex, k: int) -> "TwoTowerRetrieval":
         """Split a trained TwoTower's single EBC into the two collections and
         take over its projections. Tables and projections are shared with
         ``two_tower``, not copied, so the towers follow further training; the
@@ -163,16 +165,23 @@ class TwoTowerRetrieval(nn.Module):
 
 @torch.no_grad()
 def build_candidate_index(
-    two_tower: TwoTower, item_kjt_batches: Iterable[KeyedJaggedTensor], index: FlatIndex
-) -> FlatIndex:
+    two_tower: TwoTower, item_kjt_batches: Iterable[KeyedJaggedTensor], index: KnnIndex
+) -> KnnIndex:
     """Run the candidate tower over batches of items (one id per row and
     candidate feature) and add the embeddings to ``index`` under the ids of the
-    first candidate feature."""
+    first candidate feature. An index that has to be trained and is not yet is
+    trained on all of those embeddings first."""
     cf = two_tower._candidate_features
     ebc = _tower_ebc(two_tower.ebc, cf)
-    for kjt in item_kjt_batches:
-        emb = two_tower.candidate_proj(_tower_input(ebc, cf, kjt))
-        index.add(emb, ids=kjt[cf[0]].values())
+    embedded = (
+        (two_tower.candidate_proj(_tower_input(ebc, cf, kjt)), kjt[cf[0]].values())
+        for kjt in item_kjt_batches
+    )
+    if not getattr(index, "is_trained", True):
+        embedded = list(embedded)
+        index.train(torch.cat([emb for emb, _ in embedded]))
+    for emb, ids in embedded:
+        index.add(emb, ids=ids)
     return index
 
 

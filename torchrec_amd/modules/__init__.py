@@ -15,5 +15,5 @@ from torchrec_amd.modules.fused_embedding_modules import (  # noqa: F401
     FusedEmbeddingBagCollection,
     FusedEmbeddingCollection,
 )
-from torchrec_amd.modules.knn_index import FlatIndex  # noqa: F401
+from torchrec_amd.modules.knn_index import FlatIndex, IVFFlatIndex  # noqa: F401
 from torchrec_amd.modules.mlp import MLP, Perceptron  # noqa: F401

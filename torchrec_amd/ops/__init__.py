@@ -642,6 +642,99 @@ def mips_topk(
     return top.contiguous(), ids.contiguous()
 
 
+# ------------------------------------------------------------------------
+# IVF-Flat fine stage: top-k restricted to probed lists (csrc/ivf_topk.hip)
+# ------------------------------------------------------------------------
+
+IVF_TOPK_MAX_PROBE = 128
+IVF_TOPK_MAX_LISTS = 65536
+
+
+def ivf_topk(
+    queries: torch.Tensor,
+    corpus: torch.Tensor,
+    list_offsets: torch.Tensor,
+    probes: torch.Tensor,
+    k: int,
+    row_bias: Optional[torch.Tensor] = None,
+    splits: int = 0,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k of ``queries @ corpus.T (+ row_bias)`` per query among the rows of
+    the lists it probes.
+
+    queries, corpus, row_bias, k and the order of the result are those of
+    ``mips_topk``. The corpus is stored list by list: list l is rows
+    ``[list_offsets[l], list_offsets[l + 1])`` of it, list_offsets int64
+    [nlist + 1], non-decreasing from 0 to N, empty lists allowed. probes int64
+    [B, nprobe] names each query's lists; -1 is "no list", the other entries of
+    a row must be distinct. Returns (scores fp32 [B, k], rows int64 [B, k]);
+    where the probed lists hold fewer than k rows the tail is -inf / -1.
+    ``splits`` forces the number of row ranges a list is cut into on the GPU
+    (0: from the shapes); it does not change the result.
+
+    GPU: a device-side plan turns the probes list-major, then each list is read
+    once per 32 queries that probe it by the fused score-and-select MFMA
+    kernel; no host synchronisation. CPU: the masked fp32 score matrix and a
+    stable sort.
+    """
+    if queries.dim() != 2 or corpus.dim() != 2:
+        raise ValueError("ivf_topk: queries [B, D] and corpus [N, Dp] must be 2-D")
+    (B, D), (N, Dp) = queries.shape, corpus.shape
+    if not 1 <= D <= MIPS_TOPK_MAX_D:
+        raise ValueError(f"ivf_topk: embedding width {D} is outside 1..{MIPS_TOPK_MAX_D}")
+    if not 1 <= k <= MIPS_TOPK_MAX_K:
+        raise ValueError(f"ivf_topk: k = {k} is outside 1..{MIPS_TOPK_MAX_K}")
+    if Dp % 32 != 0 or Dp != (D + 31) // 32 * 32:
+        raise ValueError(
+            f"ivf_topk: corpus width {Dp} must be D = {D} rounded up to a multiple of 32"
+        )
+    if corpus.dtype != torch.bfloat16 or not corpus.is_contiguous():
+        raise ValueError("ivf_topk: corpus must be a contiguous bf16 tensor")
+    if queries.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("ivf_topk: queries must be fp32 or bf16")
+    if row_bias is not None and (row_bias.shape != (N,) or row_bias.dtype != torch.float32):
+        raise ValueError("ivf_topk: row_bias must be an fp32 [N] tensor")
+    if (
+        list_offsets.dim() != 1
+        or list_offsets.dtype != torch.int64
+        or not 1 <= list_offsets.numel() - 1 <= IVF_TOPK_MAX_LISTS
+    ):
+        raise ValueError(
+            f"ivf_topk: list_offsets must be int64 [nlist + 1], nlist in 1..{IVF_TOPK_MAX_LISTS}"
+        )
+    if (
+        probes.dim() != 2
+        or probes.dtype != torch.int64
+        or probes.shape[0] != B
+        or not 1 <= probes.shape[1] <= IVF_TOPK_MAX_PROBE
+    ):
+        raise ValueError(
+            f"ivf_topk: probes must be int64 [B, nprobe], nprobe in 1..{IVF_TOPK_MAX_PROBE}"
+        )
+    if queries.is_cuda:
+        hip_ops()
+        return torch.ops.trec_amd.ivf_topk(
+            queries, corpus, list_offsets, probes, row_bias, k, splits
+        )
+    nlist = list_offsets.numel() - 1
+    scores = queries.bfloat16().float() @ corpus[:, :D].float().t()
+    if row_bias is not None:
+        scores = scores + row_bias
+    # list of every row (empty lists own none), then one extra column for -1
+    row_list = torch.searchsorted(list_offsets[1:].contiguous(), torch.arange(N), right=True)
+    probed = torch.zeros(B, nlist + 1, dtype=torch.bool)
+    probed.scatter_(1, torch.where(probes < 0, nlist, probes), True)
+    scores = scores.masked_fill(~probed[:, :nlist][:, row_list], float("-inf"))
+    top, ids = torch.sort(scores, dim=1, descending=True, stable=True)
+    top, ids = top[:, :k], ids[:, :k]
+    if N < k:
+        pad = (B, k - N)
+        top = torch.cat([top, top.new_full(pad, float("-inf"))], dim=1)
+        ids = torch.cat([ids, ids.new_full(pad, -1)], dim=1)
+    ids = ids.masked_fill(top == float("-inf"), -1)
+    return top.contiguous(), ids.contiguous()
+
+
 class _FusedBceWithLogits(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels):  # type: ignore[override]

@@ -195,6 +195,12 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> lowrank_cross_bwd(
 std::tuple<at::Tensor, at::Tensor> mips_topk(const at::Tensor& queries, const at::Tensor& corpus,
                                              const c10::optional<at::Tensor>& row_bias, int64_t k,
                                              int64_t splits);
+// ivf_topk.hip
+std::tuple<at::Tensor, at::Tensor> ivf_topk(const at::Tensor& queries, const at::Tensor& corpus,
+                                            const at::Tensor& list_offsets,
+                                            const at::Tensor& probes,
+                                            const c10::optional<at::Tensor>& row_bias, int64_t k,
+                                            int64_t splits);
 // qcomm_codec.hip
 at::Tensor qcomm_mx_encode(const at::Tensor& src, int64_t fmt, const at::Tensor& col_off,
                            int64_t B);
@@ -364,6 +370,9 @@ TORCH_LIBRARY(trec_amd, m) {
   m.def(
       "mips_topk(Tensor queries, Tensor corpus, Tensor? row_bias, int k, int splits=0)"
       " -> (Tensor scores, Tensor ids)");
+  m.def(
+      "ivf_topk(Tensor queries, Tensor corpus, Tensor list_offsets, Tensor probes,"
+      " Tensor? row_bias, int k, int splits=0) -> (Tensor scores, Tensor rows)");
   m.def("qcomm_mx_encode(Tensor src, int fmt, Tensor col_off, int B) -> Tensor");
   m.def("qcomm_mx_decode(Tensor wire, Tensor(a!) out, int fmt, Tensor col_off, int B) -> ()");
   // weight_format: 0 MXFP8 (codes [N, Kp]), 1 MXFP4 (codes [N, Kp / 2])
@@ -433,6 +442,7 @@ TORCH_LIBRARY_IMPL(trec_amd, CUDA, m) {
   m.impl("lowrank_cross_fwd", trec_amd::lowrank_cross_fwd);
   m.impl("lowrank_cross_bwd", trec_amd::lowrank_cross_bwd);
   m.impl("mips_topk", trec_amd::mips_topk);
+  m.impl("ivf_topk", trec_amd::ivf_topk);
   m.impl("qcomm_mx_encode", trec_amd::qcomm_mx_encode);
   m.impl("qcomm_mx_decode", trec_amd::qcomm_mx_decode);
   m.impl("mx_linear_pack_weight", trec_amd::mx_linear_pack_weight);
